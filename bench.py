@@ -4,6 +4,7 @@
     python bench.py [--gpus N] [--steps K] [--warmup W]
     python bench.py --frame re10k [--gpus N]      BASELINE config 4: ONE full frame strong-scaled over N ranks + gather
     python bench.py --train [--precision f16]     BASELINE config 5: the training iteration (see train_bench)
+    python bench.py ... --dump-outputs DIR        also write what the last timed step returned, DIR/<name>.npy (dump_outputs)
 
 ``--gpus N`` with N > 1 needs no wrapper: when no launcher has set WORLD_SIZE, bench.py starts N fresh rank processes
 itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT in their environment) BEFORE anything in
@@ -263,6 +264,44 @@ def emit(full):
         os.write(_RESULT_FD, data)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(outputs, directory, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: ``outputs`` (what the timed path's last step returned: a dict of tensors / arrays / scalars, nested
+    dicts joined with '.') to ``directory``/<name>.npy -- float64 stays float64, everything else becomes float32.  If the
+    arrays together exceed ``limit`` bytes, each is cut to the same fraction of its elements: a sorted sample of flat indices
+    drawn from a RandomState seeded with DUMP_SAMPLE_SEED, so two runs with the same arguments write the same elements.
+    -> {name: shape written}"""
+    flat = {}
+
+    def walk(prefix, value):
+        if isinstance(value, dict):
+            for k in sorted(value):
+                walk(f'{prefix}.{k}' if prefix else str(k), value[k])
+        elif value is not None:
+            if isinstance(value, torch.Tensor):          # (bf16 has no numpy type: converted on the torch side)
+                value = value.detach().cpu()
+                value = (value if value.dtype == torch.float64 else value.float()).numpy()
+            value = numpy.asarray(value)
+            flat[prefix or 'output'] = value.astype(numpy.float64 if value.dtype == numpy.float64 else numpy.float32)
+
+    walk('', outputs)
+    total = sum(a.nbytes for a in flat.values())
+    keep = min(1.0, limit / total) if total else 1.0
+    os.makedirs(directory, exist_ok=True)
+    written = {}
+    for name, a in flat.items():
+        if keep < 1.0:
+            count = int(a.size * keep)
+            idx = numpy.sort(numpy.random.RandomState(DUMP_SAMPLE_SEED).choice(a.size, count, replace=False))
+            a = a.reshape(-1)[idx]
+        numpy.save(os.path.join(directory, name + '.npy'), a)
+        written[name] = a.shape
+    return written
+
+
 def progress(text):
     """--verbose: one line on stderr per phase (a long --extras run shows where it is).  Silent otherwise."""
     if VERBOSE:
@@ -460,9 +499,10 @@ def settle(run, seconds=None, gpu=True, chunk=8):
     return runs, time.perf_counter() - t0
 
 
-def timed_steps(step, steps, fence, gpu=True):
+def timed_steps(step, steps, fence, gpu=True, keep_last=None):
     """EXACTLY ``steps`` steps bracketed by ``fence()`` (barrier + synchronize) on both sides.  -> (elapsed seconds over
-    the whole region, per-step device milliseconds between consecutive end-of-step marks, per-step host enqueue ms)."""
+    the whole region, per-step device milliseconds between consecutive end-of-step marks, per-step host enqueue ms).
+    ``keep_last`` (a list): the last step's return value is appended to it (--dump-outputs); no other step's is held."""
     marks = [_Mark(gpu) for _ in range(steps + 1)]
     # nothing may run for the first time inside the region (on a fresh lease a first call can fault its code in from a
     # lazily loaded image): one throw-away pair of marks is recorded and read before the opening fence
@@ -474,7 +514,10 @@ def timed_steps(step, steps, fence, gpu=True):
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(steps):
-        step()
+        if keep_last is not None and i == steps - 1:
+            keep_last.append(step())
+        else:
+            step()
         marks[i + 1].record()
     fence()
     elapsed = time.perf_counter() - t0
@@ -732,7 +775,10 @@ def train_bench(args, rank, world, device, dist):
     if world == 1:
         settle(step, None, chunk=2)
     step.short_batches = 0
-    elapsed, device_ms, enqueue_ms = timed_steps(step, args.steps, fence)
+    last = [] if args.dump_outputs else None
+    elapsed, device_ms, enqueue_ms = timed_steps(step, args.steps, fence, keep_last=last)
+    if rank == 0 and last:
+        dump_outputs(last[0], args.dump_outputs)
     ranks = per_rank_table([_quantiles(device_ms)['p50'], elapsed], dist, device)
     elapsed = max_over_ranks(elapsed, dist, device)
     if rank == 0:
@@ -814,6 +860,8 @@ def frame_bench(args, rank, world, device, dist, make_renderer, data):
     if rank != 0:
         return
     assert out is not None and all(numpy.asarray(v).size > 0 for v in out.values())
+    if args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
     entry = frame_entry(args.frame, args.precision, elapsed, rays, args.steps, world)
     per = -(-rays // world)
     line = {'metric': 'rays/sec, full frame (64+128 samples, 8x256 coarse+fine) incl. raygen, gather and display output',
@@ -833,8 +881,9 @@ def frame_bench(args, rank, world, device, dist, make_renderer, data):
 
 
 # ---------------------------------------------------------------------------------------------- headline
-def measure_headline(renderer, steps, warmup, fence, world, do_settle=True):
-    """settle -> warm-up (event hooks on) -> timed region.  -> dict of raw measurements for ``headline_line``."""
+def measure_headline(renderer, steps, warmup, fence, world, do_settle=True, keep_last=None):
+    """settle -> warm-up (event hooks on) -> timed region.  -> dict of raw measurements for ``headline_line``.
+    ``keep_last``: see ``timed_steps``."""
     with torch.no_grad():
         settle_info = settle(renderer.local, None, renderer.gpu) if do_settle else None
         renderer.profile(4 * (steps + warmup) + 16)
@@ -844,7 +893,7 @@ def measure_headline(renderer, steps, warmup, fence, world, do_settle=True):
         renderer.profile_reset()
         if renderer.collective:
             renderer.gather_marks = []          # from here on every step brackets its gather with two events
-        elapsed, device_ms, enqueue_ms = timed_steps(renderer.step, steps, fence, renderer.gpu)
+        elapsed, device_ms, enqueue_ms = timed_steps(renderer.step, steps, fence, renderer.gpu, keep_last)
     gather_ms = [a.ms_until(b) for a, b in (renderer.gather_marks or [])]
     renderer.gather_marks = None
     launch_ms, launch_samples, dropped = renderer.profile_collect()
@@ -865,7 +914,10 @@ def render_bench(args, rank, world, device, dist, make_renderer, data):
             torch.cuda.synchronize()
 
     renderer = make_renderer(args.precision, 'headline')
-    m = measure_headline(renderer, args.steps, args.warmup, fence, world)
+    last = [] if args.dump_outputs else None
+    m = measure_headline(renderer, args.steps, args.warmup, fence, world, keep_last=last)
+    if rank == 0 and last:
+        dump_outputs(last[0], args.dump_outputs)
     if rank == 0:
         progress(f'headline timed: {m["elapsed"] / args.steps * 1e3:.3f} ms/step')
     ranks = None
@@ -982,6 +1034,9 @@ def main(argv=None, renderer_cls=None, backend='nccl', share_devices=False, scri
     ap.add_argument('--extra-file', default=None,
                     help='side file for the full record (default: gpurun_out/bench_extra.json under the repo)')
     ap.add_argument('--verbose', action='store_true', help='progress lines and library chatter on stderr (default: none)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one returned (rank 0) as DIR/<name>.npy, float32 or float64, '
+                         f'at most {DUMP_LIMIT_BYTES >> 20} MB in all (see dump_outputs)')
     ap.add_argument('--cpu-threads', type=int, default=None, help='threads of the CPU baseline leg (default: the cores this job owns)')
     ap.add_argument('--global-rows', type=int, default=None,
                     help='--train: ONE batch of that many rows over the N ranks (BASELINE config 5 as stated: 4096; scaling: strong)')
@@ -1005,6 +1060,8 @@ def main(argv=None, renderer_cls=None, backend='nccl', share_devices=False, scri
         args.steps = 5 if args.frame else 50
     if args.warmup is None:
         args.warmup = 1 if args.frame else 5
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f'--steps {args.steps} --warmup {args.warmup}: at least one timed step, no negative warm-up')
     standin = renderer_cls is not None
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:

@@ -213,6 +213,34 @@ def test_bench_force_collective_runs_the_multi_rank_protocol_with_one_rank(mode)
         assert line['also_measured_frame']['collective']['ranks'] == 1
 
 
+@pytest.mark.parametrize('ranks', [1, 2])
+def test_bench_dump_outputs_holds_the_last_timed_steps_arrays(ranks, tmp_path):
+    """``--dump-outputs DIR``: after the timed steps rank 0 writes what the last one returned -- the gathered per-ray colour and
+    depth over every rank -- as DIR/<name>.npy in float32; a second run with the same arguments writes the same arrays."""
+    import numpy
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f'run{run}'
+        _, line = _run_bench(ranks, '--steps', '3', '--warmup', '1', '--dump-outputs', str(out))
+        assert line['steps'] == 3 and len(line['timing']['step_trace_ms']) == 3
+        assert sorted(os.listdir(out)) == ['depth_fine.npy', 'rgb_fine.npy']
+        dumps.append({k: numpy.load(out / f'{k}.npy') for k in ('rgb_fine', 'depth_fine')})
+    idx = numpy.arange(ranks * 1024, dtype=numpy.float32)
+    assert dumps[0]['rgb_fine'].dtype == numpy.float32 and dumps[0]['depth_fine'].dtype == numpy.float32
+    assert numpy.array_equal(dumps[0]['rgb_fine'], numpy.stack([idx, 2 * idx, 3 * idx], 1))
+    assert numpy.array_equal(dumps[0]['depth_fine'], idx + 0.5)
+    assert all(numpy.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+
+
+def test_bench_dump_outputs_in_frame_mode(tmp_path):
+    """``--frame NAME --dump-outputs DIR``: the last timed frame's host arrays (here the stand-in's two) as float32."""
+    import numpy
+    _run_bench(2, '--frame', 're10k', '--steps', '2', '--warmup', '1', '--dump-outputs', str(tmp_path))
+    idx = numpy.arange(37 * 41, dtype=numpy.float32)
+    assert numpy.array_equal(numpy.load(tmp_path / 'image.npy'), numpy.stack([idx, 2 * idx, 3 * idx], 1))
+    assert numpy.array_equal(numpy.load(tmp_path / 'depth.npy'), idx + 0.5)
+
+
 def test_bench_refuses_more_ranks_than_gpus():
     """bench.py proper (no rehearsal switches): ``--gpus 2`` on a node with fewer than two GPUs is an error BEFORE any rank is
     started, and a launcher-provided rank whose LOCAL_RANK has no device of its own is an error before the process group is

@@ -438,6 +438,34 @@ def test_bench_stdout_line_is_short_whatever_the_record_holds(tmp_path, capfd):
         assert 'profiles/pmc_traffic.json @ ' in line['roofline']['traffic_source']
 
 
+def test_bench_dump_outputs_types_names_and_budget(tmp_path):
+    """bench.dump_outputs: nested dict keys joined with '.', float64 kept, every other dtype written as float32; above the byte
+    budget every array is cut to the same fraction of its elements by a seeded sample, identical from call to call."""
+    bench = _bench_module()
+    outputs = {'rgb': torch.arange(12, dtype=torch.float32).reshape(4, 3), 'image': numpy.arange(6, dtype=numpy.uint8),
+               'loss': {'total': numpy.float64(0.25)}, 'none': None}
+    written = bench.dump_outputs(outputs, str(tmp_path / 'a'))
+    assert written == {'image': (6,), 'loss.total': (), 'rgb': (4, 3)}
+    assert numpy.load(tmp_path / 'a' / 'rgb.npy').dtype == numpy.float32
+    assert numpy.load(tmp_path / 'a' / 'image.npy').dtype == numpy.float32
+    assert numpy.load(tmp_path / 'a' / 'loss.total.npy').dtype == numpy.float64
+    big = {'x': numpy.arange(4000, dtype=numpy.float32), 'y': numpy.arange(2000, dtype=numpy.float64)}
+    limit = 8000                                # a quarter of the 32000 bytes
+    for run in ('b', 'c'):
+        bench.dump_outputs(big, str(tmp_path / run), limit=limit)
+    x, y = (numpy.load(tmp_path / 'b' / f'{k}.npy') for k in 'xy')
+    assert x.nbytes + y.nbytes <= limit and x.size == 1000 and y.size == 500
+    assert numpy.all(numpy.diff(x) > 0) and numpy.isin(x, big['x']).all()
+    assert numpy.array_equal(x, numpy.load(tmp_path / 'c' / 'x.npy')) and numpy.array_equal(y, numpy.load(tmp_path / 'c' / 'y.npy'))
+
+
+def test_bench_refuses_zero_timed_steps():
+    """``ms_per_step`` is the elapsed time over --steps timed steps: --steps 0 is refused before anything runs."""
+    bench = _bench_module()
+    with pytest.raises(SystemExit):
+        bench.main(['--steps', '0'])
+
+
 def test_bench_cpu_leg_uses_the_cores_the_job_owns():
     """The CPU leg's thread count: affinity mask, capped by the cgroup quota and by 16 (round 4's 256-thread leg on a 16-core
     share never finished a pass and cost the default run 45 s)."""
