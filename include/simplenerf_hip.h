@@ -130,7 +130,9 @@ enum snerf_precision {
     SNERF_PRECISION_BF16 = 3   /* the same kernels on bf16 operands (v_mfma_f32_*_bf16, 8 significand bits, fp32's exponent
                                   range): BASELINE config 5's literal dtype.  No range limit -- nothing below under "Range"
                                   applies -- at 3 fewer significand bits than SNERF_PRECISION_F16; saved activations and layer
-                                  gradients both bf16.  Own tolerances (tests/test_gpu_bf16.py) */
+                                  gradients both bf16.  Own tolerances (tests/test_gpu_bf16.py).  Also built for every MLP
+                                  shape of the layered path (mlp_generic_bf16.hip), where SNERF_PRECISION_BF16S8 is this mode
+                                  bit for bit; the fp16 modes are refused for those shapes */
 };
 /* Range: both fp16 modes hold hidden activations and weights as fp16 numbers (pairs), so their magnitudes must stay
  * below 65504 -- far above what a NeRF MLP on encoded inputs produces (trained hidden units are O(1..100)).  Exceeding it
@@ -174,7 +176,9 @@ int snerf_mlp_forward(const snerf_mlp_desc* desc, const float* packed, const flo
  *                a separate add launch per tensor).  Sums over samples are taken in a fixed order: bit-reproducible
  *   precision    SNERF_PRECISION_FP32; SNERF_PRECISION_F16X3 for the fp16-split forward_train / dgrad chain / large
  *                weight-gradient products (the small head and encoding products stay on the fp32 matrix cores); or
- *                SNERF_PRECISION_F16 (16-bit mode).  The layout of saved_acts depends on the precision: pass to
+ *                SNERF_PRECISION_F16 (16-bit mode).  MLP shapes outside the fused kernels' set (the layered path) take
+ *                SNERF_PRECISION_FP32, SNERF_PRECISION_BF16 and SNERF_PRECISION_BF16S8 (= BF16 there) and refuse the
+ *                fp16 modes.  The layout of saved_acts depends on the precision: pass to
  *                snerf_mlp_backward the precision that snerf_mlp_forward_train was called with (both buffer-size
  *                queries are valid for every precision)
  * Inputs (rays, depths, view directions) receive no gradient -- the reference detaches the sample depths (:312).

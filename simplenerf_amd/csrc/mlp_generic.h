@@ -1,6 +1,7 @@
 // The layered MLP path (mlp_generic.hip): plan + entry points used by the C-ABI functions when build_plan (mlp_plan.h)
 // reports a shape the fused kernels are not built for.
 #pragma once
+#include <algorithm>
 #include <vector>
 
 #include "snerf_common.h"
@@ -34,6 +35,19 @@ size_t generic_backward_workspace_floats(const GenericPlan& p, long long total);
 int generic_backward(const GenericPlan& p, const float* packed, const float* acts, const float* sigma, const float* rgb,
                      const float* d_sigma, const float* d_rgb, long long total, float* workspace, float* const* grads, int precision,
                      int accumulate, hipStream_t stream);
+
+// the bf16-operand variant (mlp_generic_bf16.hip): forward over `total` consecutive samples starting at sample `first` of the call
+// (acts: `total` rows of the activation matrix, sized as generic_saved_floats says), and the whole backward (workspace sized as
+// generic_backward_workspace_floats says)
+int generic_forward_rows_bf16(const GenericPlan& p, const float* packed, const float* origins, const float* dirs, const float* view_dirs,
+                              const float* depths, long long first, long long total, int samples, const float* noise, float* sigma,
+                              float* rgb, float* acts, hipStream_t stream);
+int generic_backward_bf16(const GenericPlan& p, const float* packed, const float* acts, const float* sigma, const float* rgb,
+                          const float* d_sigma, const float* d_rgb, long long total, float* workspace, float* const* grads,
+                          int accumulate, hipStream_t stream);
+
+// row chunks the weight-gradient products of the backward are split into (fixed-order reduction)
+inline int generic_wgrad_splits(long long total) { return (int)std::min<long long>(64, std::max<long long>(1, total / 8192)); }
 
 // build_plan said "unsupported": is it a shape the layered path takes?  (fills *plan when so)
 inline bool generic_takes(const snerf_mlp_desc* desc, GenericPlan* plan) { return generic_plan(desc, plan) == SNERF_OK; }

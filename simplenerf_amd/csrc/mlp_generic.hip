@@ -17,7 +17,8 @@
 //
 // Bound: MFMA fp32 for the wide layers (2 x 4 B x width per sample and layer over HBM against 2 x width^2 FLOP: MFMA-bound from
 // width ~100 up), at the efficiency of a plain LDS-tiled GEMM -- a fallback for generality, not the headline path.
-// Always fp32 arithmetic: the fp16 / bf16 modes are refused for these shapes.  The inference entry point has no workspace
+// This file is the fp32 arithmetic; the bf16 modes run the same layers on bf16 operands (mlp_generic_bf16.hip), the fp16 modes are
+// refused for these shapes.  The inference entry point has no workspace
 // argument in the ABI, so this path keeps a per-device scratch arena for it (allocated on first use, grown when needed: a
 // FIRST generic inference call inside a graph capture fails with SNERF_E_HIP).
 #include <algorithm>
@@ -26,6 +27,7 @@
 
 #include "mlp_device.h"
 #include "mlp_generic.h"
+#include "mlp_generic_kernels.h"
 
 namespace {
 
@@ -478,31 +480,6 @@ __global__ void __launch_bounds__(256, 2) gemm_vec_kernel(GemmArgs g) {
     }
 }
 
-// out[m][n] (+)= sum_z partial[z][m][n] in z order (bit-reproducible)
-__global__ void __launch_bounds__(256) reduce_splits_kernel(const float* __restrict__ partial, long long split_stride, int splits,
-                                                            long long count, float* __restrict__ out, int accumulate) {
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += stride) {
-        float s = accumulate ? out[e] : 0.0f;
-        for (int z = 0; z < splits; ++z) s += partial[z * split_stride + e];
-        out[e] = s;
-    }
-}
-
-// column sums of dZ (N x cols, row stride ld) over a chunk of rows: partial[z][col]
-__global__ void __launch_bounds__(256) colsum_kernel(const float* __restrict__ dz, long long ld, long long rows, int cols,
-                                                     long long rows_per_split, float* __restrict__ partial) {
-    const int col = blockIdx.x * 64 + (threadIdx.x & 63), part = threadIdx.x >> 6;
-    const long long lo = (long long)blockIdx.y * rows_per_split, hi = lo + rows_per_split < rows ? lo + rows_per_split : rows;
-    float s = 0.0f;
-    if (col < cols)
-        for (long long r = lo + part; r < hi; r += 4) s += dz[r * ld + col];
-    __shared__ float sh[4][64];
-    sh[part][threadIdx.x & 63] = s;
-    __syncthreads();
-    if (part == 0 && col < cols) partial[(long long)blockIdx.y * cols + col] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
-}
-
 // The same sums for rows of whole 16-byte groups (ld and cols multiples of 4, dz 16-byte aligned: every Linear layer but the
 // heads).  Round 5: the scalar kernel above kept ONE 256-byte load per wave in flight -- 614 us per call at 262 144 x 512, 0.9 TB/s,
 // 17 % of the layered backward (rocprofv3, profiles/r05_layered_kernel_stats.csv).  Here a lane owns four columns, a wave 256, the
@@ -538,113 +515,12 @@ __global__ void __launch_bounds__(512) colsum4_kernel(const float* __restrict__ 
     }
 }
 
-// ------------------------------------------------------------------------------------------------------ encoding + heads
-// [x, sin(2^0 x), cos(2^0 x), sin(2^1 x), ...] (PositionalEncoder :533-557) with the fused kernels' exact range reduction
-struct EncodeArgs {
-    const float *origins, *dirs, *view_dirs, *depths;
-    float* acts; long long row;
-    long long total; int samples;
-    int points_degree, views_degree, pe_full, pts_in, views_pe;
-    int c_pe, c_pev, c_x5, c_v0_extra, c_v0_views;       // -1 = block absent
-};
-
-// One thread per (sample, destination column): neighbouring lanes write neighbouring columns of one row.  (Round 4's kernel gave a
-// thread a whole sample: every store of a wave went to 64 different rows -- 0.62 ms of the 8 x 512 forward at 262 144 samples,
-// profiles/r05_layered_kernel_stats.csv.  The copies of the encoding a layer input needs -- skip layer, views layer -- are computed
-// again instead of read back: same function of the same inputs, same bits.)
-__device__ __forceinline__ float encode_column(const float (&x)[3], int c) {
-    constexpr double kInvTwoPi = 0.15915494309189533576888;
-    if (c < 3) return x[c];
-    const int k = (c - 3) / 6, r = (c - 3) % 6, d = r % 3;
-    float sn, cs;
-    sincos_turns((double)x[d] * kInvTwoPi * (double)(1 << k), sn, cs);
-    return r < 3 ? sn : cs;
-}
-
-__global__ void __launch_bounds__(256) encode_kernel(EncodeArgs a) {
-    // destination blocks of a row, in order: [encoding | its first pts_in columns for the skip layer | its remaining columns for the
-    // views layer | view encoding | view encoding for the views layer]
-    const int n_pe = a.pe_full, n_x5 = a.c_x5 >= 0 ? a.pts_in : 0, n_extra = a.c_v0_extra >= 0 ? a.pe_full - a.pts_in : 0;
-    const int n_pev = a.views_pe > 0 ? a.views_pe : 0;
-    const int width = n_pe + n_x5 + n_extra + 2 * n_pev;
-    const long long count = a.total * width, stride = (long long)gridDim.x * blockDim.x;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += stride) {
-        const long long s = e / width;
-        int j = (int)(e - s * width);
-        const long long ray = s / a.samples;
-        float* row = a.acts + s * a.row;
-        int dest, c;
-        bool views = false;
-        if (j < n_pe) { dest = a.c_pe + j; c = j; }
-        else if ((j -= n_pe) < n_x5) { dest = a.c_x5 + j; c = j; }
-        else if ((j -= n_x5) < n_extra) { dest = a.c_v0_extra + j; c = a.pts_in + j; }
-        else if ((j -= n_extra) < n_pev) { dest = a.c_pev + j; c = j; views = true; }
-        else { j -= n_pev; dest = a.c_v0_views + j; c = j; views = true; }
-        float x[3];
-        if (views) {
-            for (int k = 0; k < 3; ++k) x[k] = a.view_dirs[ray * 3 + k];
-        } else {
-            const float z = a.depths[s];
-            for (int k = 0; k < 3; ++k) x[k] = a.origins[ray * 3 + k] + a.dirs[ray * 3 + k] * z;   // mul, then add (:140-142)
-        }
-        row[dest] = encode_column(x, c);
-    }
-}
-
-// pts_output / views_output rows -> sigma (N), rgb (N,3) (:664-681, :703-706)
-__global__ void __launch_bounds__(256) heads_kernel(const float* __restrict__ acts, long long row, int c_out, int c_vout, int view_dep,
-                                                    const float* __restrict__ noise, long long total, float* __restrict__ sigma,
-                                                    float* __restrict__ rgb) {
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < total; s += stride) {
-        const float* r = acts + s * row;
-        float sg = r[c_out];
-        if (noise) sg += noise[s];
-        sigma[s] = fmaxf(sg, 0.0f);
-        const float* col = view_dep ? r + c_vout : r + c_out + 1;
-        for (int c = 0; c < 3; ++c) rgb[s * 3 + c] = sigmoidf(col[c]);
-    }
-}
-
-// d sigma, d rgb -> gradients of the two head pre-activations: dout (N,4) and dvout (N,4), zero-padded
-__global__ void __launch_bounds__(256) heads_backward_kernel(const float* __restrict__ sigma, const float* __restrict__ rgb,
-                                                             const float* __restrict__ d_sigma, const float* __restrict__ d_rgb,
-                                                             long long total, int view_dep, float* __restrict__ dout,
-                                                             float* __restrict__ dvout) {
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < total; s += stride) {
-        float col[3];
-        for (int c = 0; c < 3; ++c) {
-            const float v = rgb[s * 3 + c];
-            col[c] = d_rgb[s * 3 + c] * (v * (1.0f - v));
-        }
-        dout[s * 4] = sigma[s] > 0.0f ? d_sigma[s] : 0.0f;
-        for (int c = 0; c < 3; ++c) {
-            dout[s * 4 + 1 + c] = view_dep ? 0.0f : col[c];
-            if (view_dep) dvout[s * 4 + c] = col[c];
-        }
-        if (view_dep) dvout[s * 4 + 3] = 0.0f;
-    }
-}
-
 __global__ void __launch_bounds__(256) copy_kernel(float* __restrict__ dst, const float* __restrict__ src, long long count) {
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) dst[i] = src[i];
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-// two workgroups per CU of the current device, rounded down to a multiple of eight (512 on an MI355X)
-unsigned persistent_workgroups() {
-    int device = 0, cus = 256;
-    if (hipGetDevice(&device) == hipSuccess) {
-        int value = 0;
-        if (hipDeviceGetAttribute(&value, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && value > 0) cus = value;
-    }
-    (void)hipGetLastError();
-    const unsigned count = (unsigned)(2 * cus) & ~7u;
-    return count ? count : 8u;
-}
-
 int launch_gemm(const GemmArgs& g, int splits, hipStream_t s) {
     if (g.M <= 0 || g.N <= 0) return SNERF_OK;
     // (the same arithmetic per output element either way: each is one fp32 FMA chain over k in order -- the tile only decides
@@ -743,7 +619,7 @@ int forward_rows(const GenericPlan& p, const float* packed, const float* origins
     e.views_pe = p.view_dep ? p.views_pe : 0;
     e.c_pe = p.c_pe; e.c_pev = p.c_pev; e.c_x5 = p.c_x5; e.c_v0_extra = p.view_dep && p.extra > 0 ? p.c_v0 + p.width : -1;
     e.c_v0_views = p.view_dep ? p.c_v0 + p.width + p.extra : -1;
-    hipLaunchKernelGGL(encode_kernel, dim3(snerf::stride_grid(total * (p.pe_full + (p.view_dep ? p.views_pe : 0)), 256)), dim3(256), 0, s, e);
+    hipLaunchKernelGGL(encode_kernel<float>, dim3(snerf::stride_grid(total * (p.pe_full + (p.view_dep ? p.views_pe : 0)), 256)), dim3(256), 0, s, e);
     int rc = snerf::check_launch("mlp_generic(encode)");
     if (rc != SNERF_OK) return rc;
     for (int l = 0; l < p.depth; ++l) {
@@ -864,28 +740,32 @@ size_t generic_saved_floats(const GenericPlan& p, long long total) { return (siz
 int generic_forward(const GenericPlan& p, const float* packed, const float* origins, const float* dirs, const float* view_dirs,
                     const float* depths, long long num_rays, int num_samples, const float* noise, float* sigma, float* rgb,
                     float* saved_acts, int precision, hipStream_t s) {
-    if (precision != SNERF_PRECISION_FP32)
-        return fail(SNERF_E_UNSUPPORTED, "mlp_forward: this MLP shape (width %d, views %d x %d) runs on the layered fp32 path only; "
-                                         "hip_precision must be 'fp32'", p.width, p.views_depth, p.views_width);
+    // ('bf16s8' is 'bf16' here: the fp8 saved trunk exists for the fused 256-wide kernels only)
+    const bool bf16 = precision == SNERF_PRECISION_BF16 || precision == SNERF_PRECISION_BF16S8;
+    if (precision != SNERF_PRECISION_FP32 && !bf16)
+        return fail(SNERF_E_UNSUPPORTED, "mlp_forward: this MLP shape (width %d, views %d x %d) runs on the layered path, in fp32 or "
+                                         "bf16 operands; hip_precision must be 'fp32' or 'bf16'/'bf16s8'", p.width, p.views_depth,
+                    p.views_width);
+    auto rows = bf16 ? generic_forward_rows_bf16 : forward_rows;
     const long long total = num_rays * num_samples;
     ProfileScope timed(SNERF_PROFILE_MLP_FORWARD, s, total);
     if (saved_acts)     // training: every layer's input is kept, the whole call in one pass
-        return forward_rows(p, packed, origins, dirs, view_dirs, depths, 0, total, num_samples, noise, sigma, rgb, saved_acts, s);
+        return rows(p, packed, origins, dirs, view_dirs, depths, 0, total, num_samples, noise, sigma, rgb, saved_acts, s);
     const long long rays_per_chunk = std::max(1LL, kInferenceChunk / num_samples);
     float* scratch = nullptr;
     const int rc = arena((size_t)std::min(num_rays, rays_per_chunk) * num_samples * p.row, s, &scratch);
     if (rc != SNERF_OK) return rc;
     for (long long ray = 0; ray < num_rays; ray += rays_per_chunk) {
         const long long rays = std::min(rays_per_chunk, num_rays - ray);
-        const int st = forward_rows(p, packed, origins, dirs, view_dirs, depths, ray * num_samples, rays * num_samples, num_samples,
-                                    noise, sigma, rgb, scratch, s);
+        const int st = rows(p, packed, origins, dirs, view_dirs, depths, ray * num_samples, rays * num_samples, num_samples, noise, sigma,
+                            rgb, scratch, s);
         if (st != SNERF_OK) return st;
     }
     return SNERF_OK;
 }
 
 // workspace: dZ ping-pong (2 x N x widest) | d heads (2 x N x 4) | split-K partial sums
-static int wgrad_splits(long long total) { return (int)std::min<long long>(64, std::max<long long>(1, total / 8192)); }
+static int wgrad_splits(long long total) { return generic_wgrad_splits(total); }
 
 size_t generic_backward_workspace_floats(const GenericPlan& p, long long total) {
     const long long widest = std::max({p.width, p.views_width, p.views_in, p.pts_in + p.width});
@@ -897,9 +777,12 @@ size_t generic_backward_workspace_floats(const GenericPlan& p, long long total) 
 int generic_backward(const GenericPlan& p, const float* packed, const float* acts, const float* sigma, const float* rgb,
                      const float* d_sigma, const float* d_rgb, long long total, float* workspace, float* const* grads, int precision,
                      int accumulate, hipStream_t s) {
-    if (precision != SNERF_PRECISION_FP32)
-        return fail(SNERF_E_UNSUPPORTED, "mlp_backward: this MLP shape runs on the layered fp32 path only; hip_precision must be 'fp32'");
+    const bool bf16 = precision == SNERF_PRECISION_BF16 || precision == SNERF_PRECISION_BF16S8;
+    if (precision != SNERF_PRECISION_FP32 && !bf16)
+        return fail(SNERF_E_UNSUPPORTED, "mlp_backward: this MLP shape runs on the layered path, in fp32 or bf16 operands; hip_precision "
+                                         "must be 'fp32' or 'bf16'/'bf16s8'");
     ProfileScope timed(SNERF_PROFILE_MLP_BACKWARD, s, total);
+    if (bf16) return generic_backward_bf16(p, packed, acts, sigma, rgb, d_sigma, d_rgb, total, workspace, grads, accumulate, s);
     const long long widest = std::max({p.width, p.views_width, p.views_in, p.pts_in + p.width});
     float* ping = workspace;
     float* pong = workspace + total * widest;

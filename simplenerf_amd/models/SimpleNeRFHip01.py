@@ -20,7 +20,8 @@ accumulation; ~4x faster training than fp32 at ~1e-3 agreement -- outside the fp
 ``'bf16'`` (the 16-bit mode on bf16 operands: no range limit, three significand bits fewer, tests/test_gpu_bf16.py) or
 ``'f16s8'`` (the fp16 16-bit mode with the saved trunk activations of 256-wide MLPs kept as fp8 e4m3 for the weight
 gradients: rendering and the forward are ``'f16'``'s bit for bit, the training iteration moves 15 % fewer HBM bytes;
-``'bf16s8'``: the same for the bf16 mode).
+``'bf16s8'``: the same for the bf16 mode).  MLP shapes outside the fused kernels' set (any other width, views depth > 1)
+run on the layered path in ``'fp32'`` or ``'bf16'`` (``'bf16s8'`` is ``'bf16'`` there); the fp16 modes raise for them.
 ``configs['model']['hip_fused_render']`` = ``True``: eval-mode renders of a plain coarse + fine fp32 model as one launch
 (csrc/render_fused.hip; bit-identical, off by default).
 

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""Throughput of the layered fp32 MLP path (csrc/mlp_generic.hip) on shapes the fused kernels do not cover, beside the fused
-fp32 kernel on the 8 x 256 main MLP at the same sample count: ms per call and algorithmic TFLOP/s (2 x MACs of the Linear
-layers) of the inference forward, the activation-keeping forward and the backward.
-    python tools/probes/time_layered.py [samples, default 262144]"""
+"""Throughput of the layered MLP path (csrc/mlp_generic.hip; --precision bf16: csrc/mlp_generic_bf16.hip) on shapes the fused
+kernels do not cover, beside the fused kernel of the same precision on the 8 x 256 main MLP at the same sample count: ms per
+call and algorithmic TFLOP/s (2 x MACs of the Linear layers) of the inference forward, the activation-keeping forward and the
+backward.
+    python tools/probes/time_layered.py [samples, default 262144] [--precision fp32|bf16]"""
+import argparse
 import json
 import os
 import sys
@@ -38,7 +40,11 @@ def timed(fn, reps=5):
 
 
 def main():
-    total = int(sys.argv[1]) if len(sys.argv) > 1 else 262144
+    parser = argparse.ArgumentParser()
+    parser.add_argument('samples', type=int, nargs='?', default=262144)
+    parser.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'])
+    args = parser.parse_args()
+    total, prec = args.samples, ops.PRECISIONS[args.precision]
     s = 256
     n = total // s
     gen = torch.Generator().manual_seed(0)
@@ -57,13 +63,13 @@ def main():
         mlp = ops.PackedMlp(cfg, DEV)
         mlp.pack(plist)
         flop = 2.0 * macs(cfg) * n * s
-        fwd = timed(lambda: mlp.forward(o, d, v, z, None))
-        sigma, rgb, saved = mlp.forward_train(o, d, v, z, None)
-        fwd_train = timed(lambda: mlp.forward_train(o, d, v, z, None))
+        fwd = timed(lambda: mlp.forward(o, d, v, z, None, prec))
+        sigma, rgb, saved = mlp.forward_train(o, d, v, z, None, prec)
+        fwd_train = timed(lambda: mlp.forward_train(o, d, v, z, None, prec))
         gs, gc = torch.ones_like(sigma), torch.ones_like(rgb)
         shapes = [tuple(p.shape) for p in plist]
-        bwd = timed(lambda: mlp.backward(saved, sigma, rgb, gs, gc, shapes))
-        rows.append({'mlp': label, 'samples': n * s, 'forward_ms': fwd, 'forward_tflops': flop / fwd / 1e9,
+        bwd = timed(lambda: mlp.backward(saved, sigma, rgb, gs, gc, shapes, prec))
+        rows.append({'mlp': label, 'precision': args.precision, 'samples': n * s, 'forward_ms': fwd, 'forward_tflops': flop / fwd / 1e9,
                      'forward_keeping_ms': fwd_train, 'backward_ms': bwd, 'backward_tflops': 2 * flop / bwd / 1e9,
                      'fraction_of_fp32_mfma_peak_forward': flop / fwd / 1e9 / 157.3})
         print(json.dumps(rows[-1]), flush=True)
