@@ -22,8 +22,9 @@ accumulation; ~4x faster training than fp32 at ~1e-3 agreement -- outside the fp
 gradients: rendering and the forward are ``'f16'``'s bit for bit, the training iteration moves 15 % fewer HBM bytes;
 ``'bf16s8'``: the same for the bf16 mode).  MLP shapes outside the fused kernels' set (any other width, views depth > 1)
 run on the layered path in ``'fp32'`` or ``'bf16'`` (``'bf16s8'`` is ``'bf16'`` there); the fp16 modes raise for them.
-``configs['model']['hip_fused_render']`` = ``True``: eval-mode renders of a plain coarse + fine fp32 model as one launch
-(csrc/render_fused.hip; bit-identical, off by default).
+``configs['model']['hip_fused_render']`` = ``True``: eval-mode renders of a plain coarse + fine model as one launch
+(csrc/render_fused.hip; bit-identical, off by default) -- in ``'fp32'`` (8 x 256 and 4 x 128 MLPs) and in ``'f16'``,
+``'bf16'``, ``'f16s8'``, ``'bf16s8'`` (8 x 256 MLPs); other calls take the six-launch path.
 
 Differences from the reference that a caller can observe:
   * ``model.chunk`` / ``model.netchunk`` are accepted and ignored -- the kernels tile the work themselves and the
