@@ -157,6 +157,34 @@ extern "C" int snerf_range_status(int clear) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// per-(device, stream) enqueue locks (snerf_common.h StreamLock).  One recursive mutex per pair ever locked, kept for the life of
+// the process (a thread may hold one while another looks its own up; a mutex is a few dozen bytes, one per stream that rendered).
+#include <map>
+#include <memory>
+#include <utility>
+namespace snerf {
+namespace {
+std::mutex g_stream_locks_mutex;
+std::map<std::pair<int, hipStream_t>, std::unique_ptr<std::recursive_mutex>> g_stream_locks;
+
+std::recursive_mutex* stream_mutex(hipStream_t stream) {
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) {
+        (void)hipGetLastError();
+        device = -1;          // (the call itself reports the missing device; it still enqueues nothing unlocked)
+    }
+    std::lock_guard<std::mutex> lock(g_stream_locks_mutex);
+    std::unique_ptr<std::recursive_mutex>& m = g_stream_locks[{device, stream}];
+    if (!m) m.reset(new std::recursive_mutex());
+    return m.get();
+}
+}  // namespace
+
+StreamLock::StreamLock(hipStream_t stream) : mutex(stream_mutex(stream)) { static_cast<std::recursive_mutex*>(mutex)->lock(); }
+StreamLock::~StreamLock() { static_cast<std::recursive_mutex*>(mutex)->unlock(); }
+}  // namespace snerf
+
+// ---------------------------------------------------------------------------------------------------------------
 // packed-format registry (snerf_common.h)
 #include <unordered_map>
 namespace snerf {

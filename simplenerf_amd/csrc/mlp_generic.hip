@@ -569,8 +569,8 @@ int linear_forward(const float* acts_in, float* acts_out, long long row, long lo
 }
 
 // Scratch of the inference entry point (the ABI gives it no workspace argument): one block per (device, stream), so that two
-// layered-shape forwards on different streams or threads of a device do not share an activation matrix (they used
-// to).  A block is NEVER freed or moved once handed out -- an in-flight kernel or a captured graph may hold its address; a
+// layered-shape forwards on different streams of a device do not share an activation matrix (they used to); two
+// threads on ONE stream take turns (the call holds the stream's StreamLock over all of its passes).  A block is NEVER freed or moved once handed out -- an in-flight kernel or a captured graph may hold its address; a
 // larger request on the same stream allocates another block and the old one stays (sizes are bounded by kInferenceChunk rows,
 // so a stream grows its block a handful of times at most).  Growing inside a graph capture is refused: the allocation would be
 // a synchronous call the capture cannot contain.
@@ -752,6 +752,8 @@ int generic_forward(const GenericPlan& p, const float* packed, const float* orig
     if (saved_acts)     // training: every layer's input is kept, the whole call in one pass
         return rows(p, packed, origins, dirs, view_dirs, depths, 0, total, num_samples, noise, sigma, rgb, saved_acts, s);
     const long long rays_per_chunk = std::max(1LL, kInferenceChunk / num_samples);
+    // every pass of the call writes and reads the stream's one scratch block: no other thread's pass may come in between
+    const snerf::StreamLock serialised(s);
     float* scratch = nullptr;
     const int rc = arena((size_t)std::min(num_rays, rays_per_chunk) * num_samples * p.row, s, &scratch);
     if (rc != SNERF_OK) return rc;

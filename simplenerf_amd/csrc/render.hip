@@ -36,7 +36,9 @@ struct Marching {
 // augmentation levels run on side streams beside the main levels (forward: {main coarse -> fine} | points-aug | views-aug;
 // backward: all four side by side), forked from and joined to the caller's stream with events -- still enqueue-only, and a
 // capture of the caller's stream captures the side streams with it (fork / join is what a HIP graph records as parallel
-// branches).  Side streams and events are created once per (device, caller's stream) and kept.  Above the threshold every CU is
+// branches).  Side streams and events are created once per (device, caller's stream) and kept; a call holds its stream's
+// StreamLock from the first launch to the join, so two host threads rendering on one stream never share a fork or join event
+// between their calls.  Above the threshold every CU is
 // busy with one level and the levels stay on the caller's stream, in order (two backward calls side by side measured the same
 // as back to back there: DESIGN_LOG 12.4).
 #ifndef SNERF_SIDE_BY_SIDE_SAMPLES          // (A/B builds: -DSNERF_SIDE_BY_SIDE_SAMPLES=n)
@@ -160,6 +162,8 @@ extern "C" int snerf_render_forward(const snerf_render_config* cfg, const snerf_
     if (rc != SNERF_OK) return rc;
     if (num_rays == 0) return SNERF_OK;
     const long long n = num_rays;
+    // one call's launches, side-stream forks and joins stay together against other host threads on this stream
+    const snerf::StreamLock serialised((hipStream_t)stream);
     if (cfg->fused) {
         int eligible = 0;
         rc = snerf::render_forward_fused(cfg, mlps, rays, n, out, (hipStream_t)stream, &eligible);
@@ -293,6 +297,7 @@ extern "C" int snerf_render_backward(const snerf_render_config* cfg, const snerf
     SNERF_REQUIRE(cfg->keep_activations, "render_backward: the forward must have kept the activations");
     if (num_rays == 0) return SNERF_OK;
     const long long n = num_rays;
+    const snerf::StreamLock serialised((hipStream_t)stream);
     const float* march_d = cfg->ndc ? rays->rays_d_ndc : rays->rays_d;
     size_t samples_max = 0;
     for (int l = 0; l < SNERF_RENDER_LEVELS; ++l)

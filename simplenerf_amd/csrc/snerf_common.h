@@ -70,6 +70,18 @@ int packed_formats_require(const float* packed, unsigned needed, const char* wha
 // the mask an entry point reads: precision (enum snerf_precision) x (training layout | rendering layout)
 unsigned packed_formats_needed(int precision, bool training);
 
+// Enqueue lock of one (device, stream) (api.hip; include/simplenerf_hip.h "Threads"): a call whose launches share host-side state
+// of its stream -- the side streams and fork / join events of a render, the layered path's inference scratch block -- holds it from
+// its first launch to its last, so that a second host thread enqueuing on the same stream cannot interleave with it.  Recursive:
+// snerf_render_forward holds it while the MLP entry points it calls take it again.  Host-only; adds no launch.
+struct StreamLock {
+    explicit StreamLock(hipStream_t stream);
+    ~StreamLock();
+    StreamLock(const StreamLock&) = delete;
+    StreamLock& operator=(const StreamLock&) = delete;
+    void* mutex;
+};
+
 // Grid for a grid-stride elementwise kernel: enough blocks to fill 256 CUs x 8 blocks, never more than the work.
 inline unsigned stride_grid(long long work, int block) {
     long long blocks = (work + block - 1) / block;

@@ -5,7 +5,8 @@
 :507-551): ``indices``, ``indices_mask_nerf`` [, ``indices_mask_sparse_depth``], ``iter_num``, ``num_frames``, ``rays_o``,
 ``rays_d``, ``view_dirs``, ``pixel_id``, ``target_rgb``, ``near``, ``far`` [, ``rays_o_ndc``, ``rays_d_ndc``,
 ``near_ndc``, ``far_ndc``] [, ``sparse_depth_values``, ``sparse_depth_errors``, ``sparse_depth_values_ndc``] and
-``common_data`` = {poses, intrinsics, images (each with a leading per-GPU axis), resolution}.
+``common_data`` = {poses, intrinsics, images (each with a leading per-GPU axis of ``len(configs['device'])``, default 1),
+resolution}.
 
 ``scene`` is what the reference's preprocessing leaves in ``preprocessed_data_dict`` -- dataset loading, pose
 recentring and sparse-depth rasterisation stay outside this build (out of scope):
@@ -51,6 +52,8 @@ class BatchAssembler:
         self.num_rays_sparse_depth = int(loader['sparse_depth']['num_rays']) if self.sparse_depth_needed else 0
         self.seed = int(configs.get('seed', 0))
         self.rank, self.world_size = int(rank), int(world_size)
+        devices = configs.get('device', [0])          # DataParallel's device_ids: the per-GPU axis of common_data
+        self.num_replicas = len(devices) if isinstance(devices, (list, tuple)) else 1
         t = lambda a: torch.as_tensor(a, dtype=torch.float32).to(self.device).contiguous()
         self.poses, self.intrinsics, self.images = t(scene['poses']), t(scene['intrinsics']), t(scene['images'])
         self.resolution = (int(scene['resolution'][0]), int(scene['resolution'][1]))
@@ -161,7 +164,10 @@ class BatchAssembler:
             out['indices_mask_sparse_depth'] = batch.pop('indices_mask_sparse_depth')
         out.update(iter_num=iter_num, num_frames=self.num_views)
         out.update(batch)
-        # shared tensors with the leading per-GPU axis of the reference (:545-550); a view, not a copy
-        out['common_data'] = {'poses': self.poses[None], 'intrinsics': self.intrinsics[None], 'images': self.images[None],
+        # shared tensors with the leading per-GPU axis of the reference (:545-551): one copy per entry of configs['device'], so
+        # that DataParallel's scatter hands one to each replica; an expanded view, not a copy (one device: the plain [None] view)
+        copies = self.num_replicas
+        share = (lambda t: t[None]) if copies == 1 else (lambda t: t[None].expand(copies, *t.shape))
+        out['common_data'] = {'poses': share(self.poses), 'intrinsics': share(self.intrinsics), 'images': share(self.images),
                               'resolution': self.resolution}
         return out

@@ -264,6 +264,13 @@ def train_one_iter(model, loss_computer, optimizer, input_batch: dict, sub_batch
     return totals
 
 
+def _refuse_replicated(model, who: str) -> None:
+    if isinstance(model, torch.nn.DataParallel) and len(model.device_ids) > 1:
+        raise NotImplementedError(f'{who}: a DataParallel wrapper over several devices replicates the model, scatters the batch and '
+                                  f'runs threads on every call, which a captured graph cannot replay -- capture the unwrapped model '
+                                  f'(one process per GPU, as bench.py --gpus N runs it)')
+
+
 class GraphedTrainStep:
     """The device work of one training pass -- weight re-pack, every MLP forward, compositing and resampling, the loss
     table, and the whole backward down to the parameter gradients -- captured ONCE as a HIP graph and replayed per
@@ -286,6 +293,7 @@ class GraphedTrainStep:
 
     def __init__(self, model, loss_computer, sample_batch: Dict[str, object], warmup: int = 2,
                  sub_batch_size: Optional[int] = None):
+        _refuse_replicated(model, 'GraphedTrainStep')
         self.model, self.losses = model, loss_computer
         self.static = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in sample_batch.items() if k != 'common_data'}
         self.common = dict(sample_batch.get('common_data', {}))
@@ -412,6 +420,7 @@ class GraphedIteration:
 
     def __init__(self, model, loss_computer, optimizer, batcher, lr_decayer=None, sub_batch_size: Optional[int] = None,
                  slots: int = 8, warmup: int = 1, group=None, force_collective: bool = False):
+        _refuse_replicated(model, 'GraphedIteration')
         self.world = int(getattr(batcher, 'world_size', 1))
         self.group, self.force_collective = group, bool(force_collective)
         if self.world > 1 or self.force_collective:

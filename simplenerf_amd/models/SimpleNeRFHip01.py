@@ -49,6 +49,13 @@ Differences from the reference that a caller can observe:
     9); ``alpha_*``, ``visibility_*``, ``weights_*``, ``depth_var*`` and ``z_vals_*`` are returned without a
     gradient path (the reference detaches the sample depths, :312; no loss reads the others), so a loss built only
     on them raises instead of silently training nothing.
+
+``torch.nn.DataParallel`` over several devices (the shipped demos' ``'device': [0, 1]``, src/Trainer01.py:514,
+src/Tester01.py:42): a replica -- its weights are broadcast copies, not leaves, and ``parameters()`` is empty -- returns its
+parameter gradients through autograd (the wrapper sums them onto the parameters), packs its weights into a cache of its own
+(once per forward) and, in a training forward that draws, needs ``input_batch['global_rows']`` and ``input_batch['iter_num']``
+(BatchAssembler emits both; a replica's batch without them raises).  ``set_random_draws`` refuses a replicated call.  Outputs
+equal the unwrapped model's bit for bit, gradients up to the order of the replicas' sums.
 """
 from __future__ import annotations
 
@@ -156,7 +163,9 @@ class _RenderFunction(torch.autograd.Function):
     Parameter gradients are written by the kernels straight into ``p.grad`` -- overwritten when the parameter has none
     yet, ADDED to it otherwise (the trainer's second sub-batch, src/Trainer01.py:82-96) -- instead of being returned for
     autograd to accumulate with one add launch per tensor; the Function therefore returns None for its parameter inputs.
-    ``model.return_param_grads = True`` restores the plain autograd contract (needed for torch.autograd.grad)."""
+    ``model.return_param_grads = True`` restores the plain autograd contract (needed for torch.autograd.grad), and so does a
+    call whose parameters are not leaves (a DataParallel replica, ``call.return_param_grads``): a ``.grad`` written on a
+    broadcast copy never reaches the real parameter, a RETURNED gradient flows back through the broadcast's backward."""
 
     @staticmethod
     def forward(ctx, model, call, rays, draws, *params):
@@ -188,7 +197,7 @@ class _RenderFunction(torch.autograd.Function):
         for (level, key), g in zip(ctx.layout, grad_outputs):
             if g is not None:
                 grads.setdefault(level, {})[key] = g
-        direct = not model.return_param_grads
+        direct = not (model.return_param_grads or call.return_param_grads)
         param_grads, accumulate, returned = {}, {}, []
         for level in call.levels:
             params = getattr(model, _LEVELS[level][0]).abi_params()
@@ -240,7 +249,7 @@ class SimpleNeRFHip(torch.nn.Module):
         # eval-mode renders of a plain coarse + fine model as ONE launch with the ray group's sample tile in LDS
         # (csrc/render_fused.hip; bit-identical outputs; calls outside its scope take the stage-by-stage path)
         self.fused_render = bool(mcfg.get('hip_fused_render', False))
-        self._packed: Dict[str, tuple] = {}
+        self._packed: Dict[tuple, tuple] = {}     # (MLP name, device) -> (staleness stamp, ops.PackedMlp)
         self._draws: Optional[dict] = None
         self.seed = int(configs.get('seed', 0))
         self._train_calls = 0   # training-mode forwards so far: the Philox stream of a batch that carries no 'iter_num'
@@ -338,21 +347,27 @@ class SimpleNeRFHip(torch.nn.Module):
         # the operand formats this precision reads in this mode (snerf_mlp_pack_for) leaves 9 of 25 pack launches
         # (``keeps_activations``: this call saves activations for a backward -- the storing forward and the backward read the
         # training layout, a plain render reads the rendering layout as well)
+        # (keyed by MLP and device; a model moved to another device drops its old buffers.  A DataParallel replica packs into a
+        # cache of its own, see forward: the broadcast copies are new tensors on every call, so it re-packs once per forward)
         stamp = (params[0].data_ptr(), self.precision, bool(keeps_activations)) + tuple(p._version for p in params)
-        entry = self._packed.get(name)
-        if entry is None or entry[0] != stamp or entry[1].buffer.device != params[0].device:
-            packed = entry[1] if entry is not None and entry[1].buffer.device == params[0].device \
-                else ops.PackedMlp(module.mlp_configs, params[0].device)
+        key = (name, params[0].device)
+        entry = self._packed.get(key)
+        if entry is None or entry[0] != stamp:
+            if entry is None:
+                for other in [k for k in self._packed if k[0] == name]:
+                    del self._packed[other]
+            packed = entry[1] if entry is not None else ops.PackedMlp(module.mlp_configs, params[0].device)
             packed.pack(params, self.precision, bool(keeps_activations))
-            self._packed[name] = (stamp, packed)
-        return self._packed[name][1]
+            self._packed[key] = (stamp, packed)
+        return self._packed[key][1]
 
     # ------------------------------------------------------------------------------------------
-    def _render_with_ctypes(self, batch, draws, present, packed, s_c, s_f, per_sample, with_grad):
+    def _render_with_ctypes(self, batch, draws, present, packed, s_c, s_f, per_sample, with_grad, returns):
         """ops.RenderCall (ctypes over the C ABI) + the Python autograd.Function."""
         mcfg = self.configs['model']
         call = ops.RenderCall(packed, self.ndc, bool(mcfg['white_bkgd']), bool(mcfg['lindisp']), s_c, s_f, self.precision,
                               keep_activations=with_grad, per_sample=per_sample, fused=self.fused_render)
+        call.return_param_grads = returns
         if not with_grad:
             return call.forward(batch, draws)
         params = [p for name in present if name for p in getattr(self, name).abi_params()]
@@ -368,7 +383,7 @@ class SimpleNeRFHip(torch.nn.Module):
     _EXT_KEYS = ('rgb', 'acc', 'depth', 'depth_var', 'depth_ndc', 'depth_var_ndc', 'alpha', 'visibility', 'weights', 'sigma',
                  'raw_rgb', 'raw_visibility', 'raw_visibility2', 'visibility2')     # order of `enum Key` in snerf_torch.cpp
 
-    def _render_with_extension(self, batch, draws, present, packed, s_c, s_f, per_sample, with_grad):
+    def _render_with_extension(self, batch, draws, present, packed, s_c, s_f, per_sample, with_grad, returns):
         """torch.ops.snerf.render: one dispatcher call; validation, output allocation, pointer tables and the autograd node
         live in C++ (csrc_torch/snerf_torch.cpp)."""
         snerf = _torch_ext.load()
@@ -400,7 +415,7 @@ class SimpleNeRFHip(torch.nn.Module):
                     counts[l] = len(level_params)
         try:
             res = snerf.render(cfg, descs, [None if m is None else m.buffer for m in packed], rays, draw_list, params, counts,
-                               with_grad, self.return_param_grads)
+                               with_grad, returns)
         except RuntimeError as error:        # (c10::Error; the range report keeps its own type through either binding)
             if 'outside the fp16 range' in str(error):
                 raise ops.Fp16RangeError(str(error).split('\n')[0]) from None
@@ -432,21 +447,10 @@ class SimpleNeRFHip(torch.nn.Module):
         batch = dict(input_batch)  # the caller's dict is never mutated (reference: deep_dict_copy :68)
         training = self.training
         retraw = retraw or training
-        with_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         mcfg = self.configs['model']
         rays_o = batch['rays_o']
         n = rays_o.shape[0]
         dev = rays_o.device
-        injected = self._draws
-        self._draws = None
-        noise_std = float(mcfg['raw_noise_std'])
-        perturb = bool(mcfg['perturb'] > 0.) and training
-        first_row, rows = global_rows(batch, n) if training else (0, None)
-        # the Philox stream: the batch's training iteration (shard- and sub-batch-invariant together with the global
-        # rows); a batch without one falls back to this module's count of training forwards
-        call_index = self._train_calls if batch.get('iter_num') is None else int(batch['iter_num'])
-        if training and injected is None:
-            self._train_calls += 1
 
         # which of the six MLPs take part: the augmentation models run in training mode only (:170-199, :234-263)
         present = [None] * 6
@@ -457,6 +461,36 @@ class SimpleNeRFHip(torch.nn.Module):
             for prefix, level, name in self._train_only:
                 if level == 'coarse' or self.fine_mlp_needed:
                     present[[row[0] for row in _LEVELS].index(name)] = name
+        # gradients are recorded when a tensor the kernels read requires them -- not ``self.parameters()``, which is empty in a
+        # DataParallel replica (its weights are broadcast copies held as plain attributes)
+        call_params = [getattr(self, name).abi_params() for name in present if name]
+        with_grad = torch.is_grad_enabled() and any(p.requires_grad for params in call_params for p in params)
+        # a replica (or any call on non-leaf weights) returns its parameter gradients through autograd, and keeps its packed
+        # weights and draws to itself: its __dict__ is a shallow copy of the root model's, run in one of parallel_apply's threads
+        replica = bool(self.__dict__.get('_is_replica', False)) or not call_params[0][0].is_leaf
+        if replica and not self.__dict__.get('_replica_cache', False):
+            self.__dict__.update(_packed={}, _replica_cache=True)
+        returns = self.return_param_grads or replica
+        injected = self._draws
+        if replica and injected is not None:
+            raise RuntimeError('set_random_draws: the injected draws cover the whole batch, and this DataParallel replica sees only '
+                               'its share of the rows -- inject draws into an unwrapped model (or a one-device wrapper) only')
+        self._draws = None
+        noise_std = float(mcfg['raw_noise_std'])
+        perturb = bool(mcfg['perturb'] > 0.) and training
+        if replica and training and injected is None and (perturb or noise_std > 0.):
+            for key, what in (('global_rows', 'the rows that key its jitter and density noise'),
+                              ('iter_num', 'the training iteration that keys its random stream')):
+                if input_batch.get(key) is None:
+                    raise RuntimeError(f"input_batch[{key!r}] is required by a training forward in a DataParallel replica: it "
+                                       f"gives {what} (the replica holds a slice of the batch and a copy of the model's call "
+                                       f"counter) -- BatchAssembler.get_next_batch emits it")
+        first_row, rows = global_rows(batch, n) if training else (0, None)
+        # the Philox stream: the batch's training iteration (shard- and sub-batch-invariant together with the global
+        # rows); a batch without one falls back to this module's count of training forwards
+        call_index = self._train_calls if batch.get('iter_num') is None else int(batch['iter_num'])
+        if training and injected is None:
+            self._train_calls += 1
         s_c = mcfg['coarse_mlp']['num_samples']
         s_f = mcfg['fine_mlp']['num_samples'] if self.fine_mlp_needed else 0
 
@@ -499,9 +533,11 @@ class SimpleNeRFHip(torch.nn.Module):
             if (sec_views_vis or training) and 'rays_o2' not in batch:
                 batch['rays_o2'] = self._secondary_origins(batch)          # (n, num_frames - 1, 3), :122-133
         if self.host_binding == 'torch_ext':
-            z_coarse, z_fine, out_levels = self._render_with_extension(batch, draws, present, packed, s_c, s_f, per_sample, with_grad)
+            z_coarse, z_fine, out_levels = self._render_with_extension(batch, draws, present, packed, s_c, s_f, per_sample, with_grad,
+                                                                       returns)
         else:
-            z_coarse, z_fine, out_levels = self._render_with_ctypes(batch, draws, present, packed, s_c, s_f, per_sample, with_grad)
+            z_coarse, z_fine, out_levels = self._render_with_ctypes(batch, draws, present, packed, s_c, s_f, per_sample, with_grad,
+                                                                    returns)
 
         out: Dict[str, Tensor] = {}
 
