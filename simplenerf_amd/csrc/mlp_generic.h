@@ -16,16 +16,26 @@ struct GenericPlan {
     int num_params = 0;
     std::vector<long long> w_off, w_count;   // parameter i in the "packed" buffer (ABI order, plain copies)
     long long packed_floats = 0;
-    // activation row (floats per sample) and the column of every block in it
-    long long row = 0;
-    int c_pe = 0, c_pev = 0, c_x5 = -1, c_v0 = 0, c_out = 0, c_vout = 0;
-    std::vector<int> c_h, c_hv;
+    long long row = 0;                       // floats per sample of the fp32 activation row: the matrix of either format fits in N x row
     bool skip_layer(int l) const { return l == 5 && depth > 5; }   // its input is [encoding | H_4] (:580, :662-663)
     int layer_in_dim(int l) const { return l == 0 ? pts_in : (skip_layer(l) ? pts_in + width : width); }
-    int layer_in_col(int l) const { return l == 0 ? c_pe : (skip_layer(l) ? c_x5 : c_h[l - 1]); }
+};
+
+// The activation row of one operand format (elements of that format per sample).  Blocks in layer order, each starting at a multiple
+// of `align` elements (16 bytes: the GEMMs stage 16 bytes at a time); the skip layer's input is ONE block [encoding | H_4].  The
+// heads' fp32 outputs are columns c_out.. and c_vout.. of rows head_rs floats apart: of the row itself (heads_in_row: fp32), or of
+// an fp32 [N][8] block after the matrix (bf16).
+struct GenericRow {
+    long long row = 0;
+    int c_pe = 0, c_pev = 0, c_x5 = -1, c_v0 = 0;
+    std::vector<int> c_h, c_hv;
+    int c_out = 0, c_vout = 4;
+    long long head_rs = 8;
+    int layer_in_col(const GenericPlan& p, int l) const { return l == 0 ? c_pe : (p.skip_layer(l) ? c_x5 : c_h[l - 1]); }
 };
 
 int generic_plan(const snerf_mlp_desc* desc, GenericPlan* out);
+GenericRow generic_row(const GenericPlan& p, int align, bool heads_in_row);
 int generic_pack(const GenericPlan& p, const float* const* params, float* packed, hipStream_t stream);
 size_t generic_saved_floats(const GenericPlan& p, long long total);
 int generic_forward(const GenericPlan& p, const float* packed, const float* origins, const float* dirs, const float* view_dirs,
@@ -36,15 +46,16 @@ int generic_backward(const GenericPlan& p, const float* packed, const float* act
                      const float* d_sigma, const float* d_rgb, long long total, float* workspace, float* const* grads, int precision,
                      int accumulate, hipStream_t stream);
 
-// the bf16-operand variant (mlp_generic_bf16.hip): forward over `total` consecutive samples starting at sample `first` of the call
-// (acts: `total` rows of the activation matrix, sized as generic_saved_floats says), and the whole backward (workspace sized as
-// generic_backward_workspace_floats says)
-int generic_forward_rows_bf16(const GenericPlan& p, const float* packed, const float* origins, const float* dirs, const float* view_dirs,
-                              const float* depths, long long first, long long total, int samples, const float* noise, float* sigma,
-                              float* rgb, float* acts, hipStream_t stream);
+// the same two calls on bf16 operands (mlp_generic_bf16.hip), routed there by generic_forward / generic_backward
+int generic_forward_bf16(const GenericPlan& p, const float* packed, const float* origins, const float* dirs, const float* view_dirs,
+                         const float* depths, long long num_rays, int num_samples, const float* noise, float* sigma, float* rgb,
+                         float* saved_acts, hipStream_t stream);
 int generic_backward_bf16(const GenericPlan& p, const float* packed, const float* acts, const float* sigma, const float* rgb,
                           const float* d_sigma, const float* d_rgb, long long total, float* workspace, float* const* grads,
                           int accumulate, hipStream_t stream);
+
+// scratch of the inference forward (mlp_generic.hip): a block of at least `floats` for the current device and this stream
+int generic_arena(size_t floats, hipStream_t stream, float** out);
 
 // row chunks the weight-gradient products of the backward are split into (fixed-order reduction)
 inline int generic_wgrad_splits(long long total) { return (int)std::min<long long>(64, std::max<long long>(1, total / 8192)); }

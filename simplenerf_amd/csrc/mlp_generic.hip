@@ -17,10 +17,11 @@
 //
 // Bound: MFMA fp32 for the wide layers (2 x 4 B x width per sample and layer over HBM against 2 x width^2 FLOP: MFMA-bound from
 // width ~100 up), at the efficiency of a plain LDS-tiled GEMM -- a fallback for generality, not the headline path.
-// This file is the fp32 arithmetic; the bf16 modes run the same layers on bf16 operands (mlp_generic_bf16.hip), the fp16 modes are
-// refused for these shapes.  The inference entry point has no workspace
-// argument in the ABI, so this path keeps a per-device scratch arena for it (allocated on first use, grown when needed: a
-// FIRST generic inference call inside a graph capture fails with SNERF_E_HIP).
+// The layer walk -- which layer reads and writes which columns with which parameters, forward and backward -- is written once
+// (mlp_generic_walk.h) for two operand formats: this file is the fp32 one (its GEMMs, its row) together with the plan, the entry
+// points and their precision gate; mlp_generic_bf16.hip is the bf16 one; the fp16 modes are refused for these shapes.  The
+// inference entry point has no workspace argument in the ABI, so this path keeps a per-device scratch arena for it (allocated on
+// first use, grown when needed: a FIRST generic inference call inside a graph capture fails with SNERF_E_HIP).
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -28,10 +29,9 @@
 #include "mlp_device.h"
 #include "mlp_generic.h"
 #include "mlp_generic_kernels.h"
+#include "mlp_generic_walk.h"
 
 namespace {
-
-using snerf::GenericPlan;
 
 // ---------------------------------------------------------------------------------------------------------------- GEMM
 struct GemmArgs {
@@ -523,22 +523,17 @@ __global__ void __launch_bounds__(256) copy_kernel(float* __restrict__ dst, cons
 // ------------------------------------------------------------------------------------------------------------ host side
 int launch_gemm(const GemmArgs& g, int splits, hipStream_t s) {
     if (g.M <= 0 || g.N <= 0) return SNERF_OK;
-    // (the same arithmetic per output element either way: each is one fp32 FMA chain over k in order -- the tile only decides
-    // which workgroup computes it)
-    // ... the large tile only where it still fills the chip twice over: a 256 x 256 weight gradient split 32 ways is 128 workgroups
-    // of 128 x 128 (22.6 -> 25.5 ms for the 8 x 256 / 2 x 128 backward before this condition)
-    const long long large_tiles = (long long)((g.N + 127) / 128) * ((g.M + 127) / 128) * (splits > 0 ? splits : 1);
-    if (g.M >= 128 && g.N >= 128 && large_tiles >= 512) {
-        const dim3 grid((g.N + 127) / 128, (g.M + 127) / 128, splits > 0 ? splits : 1);
+    int tile = 0;
+    const dim3 grid = gemm_grid(g.M, g.N, splits, &tile);
+    if (tile == 128) {
         // 16-byte staging (Stager MODE 1 / 2) where everything it touches is a multiple of four floats; the three combinations are
         // the path's three products: forward (A, B along k), input gradient (A along k, B along n), weight gradient (A along m,
         // B along n)
-        auto aligned = [](const float* ptr) { return reinterpret_cast<uintptr_t>(ptr) % 16 == 0; };
         const bool k_fours = g.K % 4 == 0 && (splits <= 0 || g.k_chunk % 4 == 0);
-        const bool a_along_k = g.a_cs == 1 && g.a_rs % 4 == 0 && aligned(g.A) && k_fours;
-        const bool a_along_m = g.a_rs == 1 && g.a_cs % 4 == 0 && aligned(g.A) && g.M % 4 == 0;
-        const bool b_along_k = g.b_rs == 1 && g.b_cs % 4 == 0 && aligned(g.B) && k_fours;
-        const bool b_along_n = g.b_cs == 1 && g.b_rs % 4 == 0 && aligned(g.B) && g.N % 4 == 0;
+        const bool a_along_k = g.a_cs == 1 && g.a_rs % 4 == 0 && aligned16(g.A) && k_fours;
+        const bool a_along_m = g.a_rs == 1 && g.a_cs % 4 == 0 && aligned16(g.A) && g.M % 4 == 0;
+        const bool b_along_k = g.b_rs == 1 && g.b_cs % 4 == 0 && aligned16(g.B) && k_fours;
+        const bool b_along_n = g.b_cs == 1 && g.b_rs % 4 == 0 && aligned16(g.B) && g.N % 4 == 0;
 #ifdef SNERF_PROBE_GEMM_SCALAR_STAGING
         hipLaunchKernelGGL((gemm_kernel<128, 128>), grid, dim3(256), 0, s, g);
 #else
@@ -551,22 +546,58 @@ int launch_gemm(const GemmArgs& g, int splits, hipStream_t s) {
         else hipLaunchKernelGGL((gemm_kernel<128, 128>), grid, dim3(256), 0, s, g);
 #endif
     } else {
-        const dim3 grid((g.N + 63) / 64, (g.M + 63) / 64, splits > 0 ? splits : 1);
         hipLaunchKernelGGL((gemm_kernel<64, 64>), grid, dim3(256), 0, s, g);
     }
     return snerf::check_launch("mlp_generic(gemm)");
 }
 
-// Y[rows, out] = act(X[rows, in] . W[out, in]^T + b): X, Y are column blocks of the activation matrix
-int linear_forward(const float* acts_in, float* acts_out, long long row, long long rows, int in, int out, const float* w,
-                   const float* b, bool relu, hipStream_t s) {
-    GemmArgs g = {};
-    g.A = acts_in; g.a_rs = row; g.a_cs = 1;
-    g.B = w; g.b_rs = 1; g.b_cs = in;
-    g.C = acts_out; g.c_rs = row; g.c_cs = 1;
-    g.bias = b; g.M = (int)rows; g.N = out; g.K = in; g.relu = relu ? 1 : 0;
-    return launch_gemm(g, 0, s);
-}
+// The fp32 operand format of the layer walk (mlp_generic_walk.h): activation row and dZ buffers of floats, every block a layer reads
+// at a multiple of four floats (so that the GEMM can stage it 16 bytes at a time, Stager MODE 1 / 2), the heads in the row.
+struct F32Operands {
+    using Act = float;
+    static constexpr const char* kName = "mlp_generic";
+    static constexpr int kAlign = 4;
+    static constexpr bool kHeadsInRow = true;
+    static long long ld(long long width) { return width; }
+    static long long floats(long long elems) { return elems; }
+
+    // Y[rows, out] = act(X[rows, in] . W[out, in]^T + b): X, Y are column blocks of the activation matrix
+    static int linear(const float* x, long long x_rs, float* y, long long y_rs, long long rows, int in, int out, const float* w,
+                      const float* b, bool relu, hipStream_t s) {
+        GemmArgs g = {};
+        g.A = x; g.a_rs = x_rs; g.a_cs = 1;
+        g.B = w; g.b_rs = 1; g.b_cs = in;
+        g.C = y; g.c_rs = y_rs; g.c_cs = 1;
+        g.bias = b; g.M = (int)rows; g.N = out; g.K = in; g.relu = relu ? 1 : 0;
+        return launch_gemm(g, 0, s);
+    }
+    static int input_grad(const float* dz, long long dz_ld, int out, const float* w, int w_ld, int cols, float* dx, long long dx_ld,
+                          bool add, const float* gate, long long gate_rs, long long rows, hipStream_t s) {
+        GemmArgs g = {};
+        g.A = dz; g.a_rs = dz_ld; g.a_cs = 1;
+        g.B = w; g.b_rs = w_ld; g.b_cs = 1;
+        g.C = dx; g.c_rs = dx_ld; g.c_cs = 1;
+        g.M = (int)rows; g.N = cols; g.K = out; g.accumulate = add ? 1 : 0;
+        g.mask = gate; g.mask_rs = gate_rs;
+        return launch_gemm(g, 0, s);
+    }
+    static int wgrad_gemm(const float* dz, long long dz_ld, int out, const float* x, long long x_rs, int in, long long total, int splits,
+                          long long k_chunk, float* partial, hipStream_t s) {
+        GemmArgs g = {};
+        g.A = dz; g.a_rs = 1; g.a_cs = dz_ld;           // A(m = out feature, k = sample) = dZ[k][m]
+        g.B = x; g.b_rs = x_rs; g.b_cs = 1;             // B(k = sample, n = in feature)
+        g.C = partial; g.c_rs = in; g.c_cs = 1;
+        g.M = out; g.N = in; g.K = (int)total; g.k_chunk = k_chunk; g.split_stride = (long long)out * in;
+        return launch_gemm(g, splits, s);
+    }
+    static int colsum(const float* dz, long long dz_ld, int out, long long total, int bsplits, long long b_chunk, float* bpart, hipStream_t s) {
+        if (out % 4 == 0 && dz_ld % 4 == 0 && aligned16(dz) && aligned16(bpart))
+            hipLaunchKernelGGL(colsum4_kernel, dim3((out + 255) / 256, bsplits), dim3(512), 0, s, dz, dz_ld, total, out, b_chunk, bpart);
+        else
+            hipLaunchKernelGGL(colsum_kernel, dim3((out + 63) / 64, bsplits), dim3(256), 0, s, dz, dz_ld, total, out, b_chunk, bpart);
+        return SNERF_OK;
+    }
+};
 
 // Scratch of the inference entry point (the ABI gives it no workspace argument): one block per (device, stream), so that two
 // layered-shape forwards on different streams of a device do not share an activation matrix (they used to); two
@@ -578,9 +609,23 @@ struct ArenaBlock { int device; hipStream_t stream; float* base; size_t floats; 
 std::mutex g_arena_mutex;
 std::vector<ArenaBlock> g_arena;
 
-int arena(size_t floats, hipStream_t stream, float** out) {
+// fp32 or bf16 operands ('bf16s8' is 'bf16' here: the fp8 saved trunk exists for the fused 256-wide kernels only): *bf16 says which.
+// The fp16 modes are refused for these shapes, not run in another precision.
+int layered_operands(const GenericPlan& p, int precision, const char* entry, bool* bf16) {
+    *bf16 = precision == SNERF_PRECISION_BF16 || precision == SNERF_PRECISION_BF16S8;
+    if (precision == SNERF_PRECISION_FP32 || *bf16) return SNERF_OK;
+    return snerf::fail(SNERF_E_UNSUPPORTED, "%s: this MLP shape (width %d, views %d x %d) runs on the layered path, in fp32 or bf16 "
+                                            "operands; hip_precision must be 'fp32' or 'bf16'/'bf16s8'", entry, p.width, p.views_depth,
+                       p.views_width);
+}
+
+}  // namespace
+
+namespace snerf {
+
+int generic_arena(size_t floats, hipStream_t stream, float** out) {
     int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return snerf::fail(SNERF_E_HIP, "mlp_forward(layered): no current HIP device");
+    if (hipGetDevice(&device) != hipSuccess) return fail(SNERF_E_HIP, "mlp_forward(layered): no current HIP device");
     std::lock_guard<std::mutex> lock(g_arena_mutex);
     for (const ArenaBlock& b : g_arena)
         if (b.device == device && b.stream == stream && b.floats >= floats) {
@@ -589,71 +634,20 @@ int arena(size_t floats, hipStream_t stream, float** out) {
         }
     hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(stream, &capturing) == hipSuccess && capturing != hipStreamCaptureStatusNone)
-        return snerf::fail(SNERF_E_UNSUPPORTED, "mlp_forward(layered): the scratch block of this stream must grow to %zu MB, which a graph "
-                                                "capture cannot contain -- run one call of this size on the stream before capturing",
-                           floats * sizeof(float) >> 20);
+        return fail(SNERF_E_UNSUPPORTED, "mlp_forward(layered): the scratch block of this stream must grow to %zu MB, which a graph "
+                                         "capture cannot contain -- run one call of this size on the stream before capturing",
+                    floats * sizeof(float) >> 20);
     (void)hipGetLastError();
     void* p = nullptr;
     const hipError_t e = hipMalloc(&p, floats * sizeof(float));
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return snerf::fail(SNERF_E_HIP, "mlp_forward(layered): scratch of %zu MB: %s", floats * sizeof(float) >> 20, hipGetErrorString(e));
+        return fail(SNERF_E_HIP, "mlp_forward(layered): scratch of %zu MB: %s", floats * sizeof(float) >> 20, hipGetErrorString(e));
     }
     g_arena.push_back({device, stream, static_cast<float*>(p), floats});
     *out = static_cast<float*>(p);
     return SNERF_OK;
 }
-
-constexpr long long kInferenceChunk = 65536;     // samples per pass of the inference entry point (bounds its scratch)
-
-// forward over `total` consecutive samples starting at sample `first` of the call; acts has `total` rows
-int forward_rows(const GenericPlan& p, const float* packed, const float* origins, const float* dirs, const float* view_dirs,
-                 const float* depths, long long first, long long total, int samples, const float* noise, float* sigma, float* rgb,
-                 float* acts, hipStream_t s) {
-    EncodeArgs e = {};
-    e.origins = origins + (first / samples) * 3; e.dirs = dirs + (first / samples) * 3;
-    e.view_dirs = view_dirs ? view_dirs + (first / samples) * 3 : nullptr;
-    // (the chunk starts at a ray boundary: kInferenceChunk is rounded to whole rays by the caller)
-    e.depths = depths + first; e.acts = acts; e.row = p.row; e.total = total; e.samples = samples;
-    e.points_degree = p.points_degree; e.views_degree = p.views_degree; e.pe_full = p.pe_full; e.pts_in = p.pts_in;
-    e.views_pe = p.view_dep ? p.views_pe : 0;
-    e.c_pe = p.c_pe; e.c_pev = p.c_pev; e.c_x5 = p.c_x5; e.c_v0_extra = p.view_dep && p.extra > 0 ? p.c_v0 + p.width : -1;
-    e.c_v0_views = p.view_dep ? p.c_v0 + p.width + p.extra : -1;
-    hipLaunchKernelGGL(encode_kernel<float>, dim3(snerf::stride_grid(total * (p.pe_full + (p.view_dep ? p.views_pe : 0)), 256)), dim3(256), 0, s, e);
-    int rc = snerf::check_launch("mlp_generic(encode)");
-    if (rc != SNERF_OK) return rc;
-    for (int l = 0; l < p.depth; ++l) {
-        rc = linear_forward(acts + p.layer_in_col(l), acts + p.c_h[l], p.row, total, p.layer_in_dim(l), p.width,
-                            packed + p.w_off[2 * l], packed + p.w_off[2 * l + 1], true, s);
-        if (rc != SNERF_OK) return rc;
-    }
-    const int po = 2 * p.depth;
-    rc = linear_forward(acts + p.c_h[p.depth - 1], acts + p.c_out, p.row, total, p.width, p.pts_out_rows, packed + p.w_off[po],
-                        packed + p.w_off[po + 1], false, s);
-    if (rc != SNERF_OK) return rc;
-    if (p.view_dep) {
-        rc = linear_forward(acts + p.c_h[p.depth - 1], acts + p.c_v0, p.row, total, p.width, p.width, packed + p.w_off[po + 2],
-                            packed + p.w_off[po + 3], false, s);                                   // feature: no activation (:683)
-        if (rc != SNERF_OK) return rc;
-        for (int j = 0; j < p.views_depth; ++j) {
-            rc = linear_forward(acts + (j == 0 ? p.c_v0 : p.c_hv[j - 1]), acts + p.c_hv[j], p.row, total,
-                                j == 0 ? p.views_in : p.views_width, p.views_width, packed + p.w_off[po + 4 + 2 * j],
-                                packed + p.w_off[po + 5 + 2 * j], true, s);
-            if (rc != SNERF_OK) return rc;
-        }
-        const int pv = po + 4 + 2 * p.views_depth;
-        rc = linear_forward(acts + p.c_hv[p.views_depth - 1], acts + p.c_vout, p.row, total, p.views_width, 3, packed + p.w_off[pv],
-                            packed + p.w_off[pv + 1], false, s);
-        if (rc != SNERF_OK) return rc;
-    }
-    hipLaunchKernelGGL(heads_kernel, dim3(snerf::stride_grid(total, 256)), dim3(256), 0, s, acts, p.row, p.c_out, p.c_vout,
-                       p.view_dep ? 1 : 0, noise ? noise + first : nullptr, total, sigma + first, rgb + first * 3);
-    return snerf::check_launch("mlp_generic(heads)");
-}
-
-}  // namespace
-
-namespace snerf {
 
 int generic_plan(const snerf_mlp_desc* d, GenericPlan* out) {
     if (!d) return fail(SNERF_E_INVALID, "mlp: NULL descriptor");
@@ -698,32 +692,30 @@ int generic_plan(const snerf_mlp_desc* d, GenericPlan* out) {
         param(3LL * p.views_width); param(3);
     }
     p.packed_floats = off;
-    // activation row
-    // (every block a Linear layer reads starts at a multiple of four floats, so that the GEMM can stage it 16 bytes at a time --
-    // Stager MODE 1 / 2; H_4 follows the skip layer's encoding copy directly, as that layer reads [encoding | H_4] as ONE input)
-    int c = 0;
-#ifdef SNERF_PROBE_GENERIC_PACKED_ROW     // A/B builds: the row of rounds 4-5, blocks back to back
-    auto four = [&]() {};
-#else
-    auto four = [&]() { c = (c + 3) / 4 * 4; };
-#endif
-    p.c_pe = c; c += p.pe_full;
-    four(); p.c_pev = c; c += p.views_pe;
-    p.c_x5 = -1;
-    p.c_h.assign(p.depth, 0);
-    for (int l = 0; l < p.depth; ++l) {
-        four();
-        if (l == 4 && p.depth > 5) { p.c_x5 = c; c += p.pts_in; }      // [encoding | H_4]: the skip layer's input (:662-663)
-        p.c_h[l] = c; c += p.width;
-    }
-    four(); p.c_v0 = c; if (p.view_dep) c += p.views_in;
-    p.c_hv.assign(p.views_depth, 0);
-    for (int j = 0; j < p.views_depth; ++j) { four(); p.c_hv[j] = c; c += p.views_width; }
-    four(); p.c_out = c; c += 4;
-    p.c_vout = c; c += 4;
-    p.row = (c + 3) / 4 * 4;
+    p.row = generic_row(p, F32Operands::kAlign, F32Operands::kHeadsInRow).row;
     *out = p;
     return SNERF_OK;
+}
+
+GenericRow generic_row(const GenericPlan& p, int align, bool heads_in_row) {
+    GenericRow r;
+    int c = 0;
+    auto next = [&]() { c = (c + align - 1) / align * align; };
+    r.c_pe = c; c += p.pe_full;
+    next(); r.c_pev = c; c += p.views_pe;
+    r.c_h.assign(p.depth, 0);
+    for (int l = 0; l < p.depth; ++l) {
+        next();
+        if (l == 4 && p.depth > 5) { r.c_x5 = c; c += p.pts_in; }      // [encoding | H_4]: the skip layer's input (:662-663)
+        r.c_h[l] = c; c += p.width;
+    }
+    next(); r.c_v0 = c; if (p.view_dep) c += p.views_in;
+    r.c_hv.assign(p.views_depth, 0);
+    for (int j = 0; j < p.views_depth; ++j) { next(); r.c_hv[j] = c; c += p.views_width; }
+    next();
+    if (heads_in_row) { r.c_out = c; r.c_vout = c + 4; c += 8; r.head_rs = c; }
+    r.row = c;
+    return r;
 }
 
 int generic_pack(const GenericPlan& p, const float* const* params, float* packed, hipStream_t s) {
@@ -740,154 +732,25 @@ size_t generic_saved_floats(const GenericPlan& p, long long total) { return (siz
 int generic_forward(const GenericPlan& p, const float* packed, const float* origins, const float* dirs, const float* view_dirs,
                     const float* depths, long long num_rays, int num_samples, const float* noise, float* sigma, float* rgb,
                     float* saved_acts, int precision, hipStream_t s) {
-    // ('bf16s8' is 'bf16' here: the fp8 saved trunk exists for the fused 256-wide kernels only)
-    const bool bf16 = precision == SNERF_PRECISION_BF16 || precision == SNERF_PRECISION_BF16S8;
-    if (precision != SNERF_PRECISION_FP32 && !bf16)
-        return fail(SNERF_E_UNSUPPORTED, "mlp_forward: this MLP shape (width %d, views %d x %d) runs on the layered path, in fp32 or "
-                                         "bf16 operands; hip_precision must be 'fp32' or 'bf16'/'bf16s8'", p.width, p.views_depth,
-                    p.views_width);
-    auto rows = bf16 ? generic_forward_rows_bf16 : forward_rows;
-    const long long total = num_rays * num_samples;
-    ProfileScope timed(SNERF_PROFILE_MLP_FORWARD, s, total);
-    if (saved_acts)     // training: every layer's input is kept, the whole call in one pass
-        return rows(p, packed, origins, dirs, view_dirs, depths, 0, total, num_samples, noise, sigma, rgb, saved_acts, s);
-    const long long rays_per_chunk = std::max(1LL, kInferenceChunk / num_samples);
-    // every pass of the call writes and reads the stream's one scratch block: no other thread's pass may come in between
-    const snerf::StreamLock serialised(s);
-    float* scratch = nullptr;
-    const int rc = arena((size_t)std::min(num_rays, rays_per_chunk) * num_samples * p.row, s, &scratch);
+    bool bf16 = false;
+    const int rc = layered_operands(p, precision, "mlp_forward", &bf16);
     if (rc != SNERF_OK) return rc;
-    for (long long ray = 0; ray < num_rays; ray += rays_per_chunk) {
-        const long long rays = std::min(rays_per_chunk, num_rays - ray);
-        const int st = rows(p, packed, origins, dirs, view_dirs, depths, ray * num_samples, rays * num_samples, num_samples, noise, sigma,
-                            rgb, scratch, s);
-        if (st != SNERF_OK) return st;
-    }
-    return SNERF_OK;
+    ProfileScope timed(SNERF_PROFILE_MLP_FORWARD, s, num_rays * num_samples);
+    auto call = bf16 ? generic_forward_bf16 : forward_call<F32Operands>;
+    return call(p, packed, origins, dirs, view_dirs, depths, num_rays, num_samples, noise, sigma, rgb, saved_acts, s);
 }
 
-// workspace: dZ ping-pong (2 x N x widest) | d heads (2 x N x 4) | split-K partial sums
-static int wgrad_splits(long long total) { return generic_wgrad_splits(total); }
-
-size_t generic_backward_workspace_floats(const GenericPlan& p, long long total) {
-    const long long widest = std::max({p.width, p.views_width, p.views_in, p.pts_in + p.width});
-    const long long biggest = std::max({(long long)p.width * (p.pts_in + p.width), (long long)p.views_width * p.views_in,
-                                        (long long)p.views_width * p.views_width, (long long)p.width * p.width});
-    return (size_t)(2 * total * widest + 8 * total + (long long)wgrad_splits(total) * (biggest + widest) + 64);
-}
+size_t generic_backward_workspace_floats(const GenericPlan& p, long long total) { return (size_t)(workspace_of<F32Operands>(p, total).end + 64); }
 
 int generic_backward(const GenericPlan& p, const float* packed, const float* acts, const float* sigma, const float* rgb,
                      const float* d_sigma, const float* d_rgb, long long total, float* workspace, float* const* grads, int precision,
                      int accumulate, hipStream_t s) {
-    const bool bf16 = precision == SNERF_PRECISION_BF16 || precision == SNERF_PRECISION_BF16S8;
-    if (precision != SNERF_PRECISION_FP32 && !bf16)
-        return fail(SNERF_E_UNSUPPORTED, "mlp_backward: this MLP shape runs on the layered path, in fp32 or bf16 operands; hip_precision "
-                                         "must be 'fp32' or 'bf16'/'bf16s8'");
+    bool bf16 = false;
+    const int rc = layered_operands(p, precision, "mlp_backward", &bf16);
+    if (rc != SNERF_OK) return rc;
     ProfileScope timed(SNERF_PROFILE_MLP_BACKWARD, s, total);
-    if (bf16) return generic_backward_bf16(p, packed, acts, sigma, rgb, d_sigma, d_rgb, total, workspace, grads, accumulate, s);
-    const long long widest = std::max({p.width, p.views_width, p.views_in, p.pts_in + p.width});
-    float* ping = workspace;
-    float* pong = workspace + total * widest;
-    float* dout = workspace + 2 * total * widest;
-    float* dvout = dout + 4 * total;
-    float* partial = dvout + 4 * total;
-    const int splits = wgrad_splits(total);
-    const long long k_chunk = (total + splits - 1) / splits;
-
-    hipLaunchKernelGGL(heads_backward_kernel, dim3(stride_grid(total, 256)), dim3(256), 0, s, sigma, rgb, d_sigma, d_rgb, total,
-                       p.view_dep ? 1 : 0, dout, dvout);
-    int rc = check_launch("mlp_generic(heads backward)");
-    if (rc != SNERF_OK) return rc;
-
-    // dW = dZ^T . X (split over the samples, fixed-order reduction), db = column sums of dZ
-    auto weight_grad = [&](const float* dz, long long dz_ld, int out, const float* x, int in, float* gw, float* gb) -> int {
-        GemmArgs g = {};
-        g.A = dz; g.a_rs = 1; g.a_cs = dz_ld;           // A(m = out feature, k = sample) = dZ[k][m]
-        g.B = x; g.b_rs = p.row; g.b_cs = 1;            // B(k = sample, n = in feature)
-        g.C = partial; g.c_rs = in; g.c_cs = 1;
-        g.M = out; g.N = in; g.K = (int)total; g.k_chunk = k_chunk; g.split_stride = (long long)out * in;
-        int st = launch_gemm(g, splits, s);
-        if (st != SNERF_OK) return st;
-        hipLaunchKernelGGL(reduce_splits_kernel, dim3(stride_grid((long long)out * in, 256)), dim3(256), 0, s, partial,
-                           (long long)out * in, splits, (long long)out * in, gw, accumulate);
-        st = check_launch("mlp_generic(reduce)");
-        if (st != SNERF_OK) return st;
-        // bias gradient = column sums of dZ.  The weight partial sums above have just been folded, so their area is free again: the
-        // column sums take four times as many row chunks as the GEMM had splits (32 chunks x two column blocks was 64 workgroups on
-        // 256 CUs: 151 us per call at 262 144 x 512, 3.6 TB/s) and put their partial rows at its start.
-        const int bsplits = in >= 4 ? splits * 4 : splits;        // (the area holds splits x out x in floats: room for splits x in rows of `out`)
-        const long long b_chunk = (total + bsplits - 1) / bsplits;
-        float* bpart = partial;
-        if (out % 4 == 0 && dz_ld % 4 == 0 && reinterpret_cast<uintptr_t>(dz) % 16 == 0 && reinterpret_cast<uintptr_t>(bpart) % 16 == 0)
-            hipLaunchKernelGGL(colsum4_kernel, dim3((out + 255) / 256, bsplits), dim3(512), 0, s, dz, dz_ld, total, out, b_chunk, bpart);
-        else
-            hipLaunchKernelGGL(colsum_kernel, dim3((out + 63) / 64, bsplits), dim3(256), 0, s, dz, dz_ld, total, out, b_chunk, bpart);
-        st = check_launch("mlp_generic(bias sums)");
-        if (st != SNERF_OK) return st;
-        hipLaunchKernelGGL(reduce_splits_kernel, dim3(1), dim3(256), 0, s, bpart, (long long)out, bsplits, (long long)out, gb, accumulate);
-        return check_launch("mlp_generic(reduce bias)");
-    };
-    // dX[:, cols] (+)= dZ . W[:, col0 : col0 + cols], then gated by the ReLU of the layer that produced X
-    auto input_grad = [&](const float* dz, long long dz_ld, int out, const float* w, int w_ld, int col0, int cols, float* dx,
-                          long long dx_ld, bool add, const float* gate) -> int {
-        GemmArgs g = {};
-        g.A = dz; g.a_rs = dz_ld; g.a_cs = 1;
-        g.B = w + col0; g.b_rs = w_ld; g.b_cs = 1;
-        g.C = dx; g.c_rs = dx_ld; g.c_cs = 1;
-        g.M = (int)total; g.N = cols; g.K = out; g.accumulate = add ? 1 : 0;
-        g.mask = gate; g.mask_rs = p.row;
-        return launch_gemm(g, 0, s);
-    };
-
-    const int po = 2 * p.depth;
-    float* dh = ping;        // gradient of the trunk's last activation H_D-1, then dZ of each trunk layer in turn
-    float* other = pong;
-    const float* h_last = acts + p.c_h[p.depth - 1];
-    if (p.view_dep) {
-        const int pv = po + 4 + 2 * p.views_depth;
-        // views head and views layers, last first
-        rc = weight_grad(dvout, 4, 3, acts + p.c_hv[p.views_depth - 1], p.views_width, grads[pv], grads[pv + 1]);
-        if (rc != SNERF_OK) return rc;
-        rc = input_grad(dvout, 4, 3, packed + p.w_off[pv], p.views_width, 0, p.views_width, other, p.views_width, false,
-                        acts + p.c_hv[p.views_depth - 1]);
-        if (rc != SNERF_OK) return rc;
-        float* dzv = other; float* spare = dh;
-        for (int j = p.views_depth - 1; j >= 0; --j) {
-            const int in = j == 0 ? p.views_in : p.views_width;
-            const float* x = acts + (j == 0 ? p.c_v0 : p.c_hv[j - 1]);
-            rc = weight_grad(dzv, p.views_width, p.views_width, x, in, grads[po + 4 + 2 * j], grads[po + 5 + 2 * j]);
-            if (rc != SNERF_OK) return rc;
-            // j > 0: d HV_j-1, gated by its ReLU; j == 0: d feature = the first `width` columns of the views input (no activation)
-            rc = input_grad(dzv, p.views_width, p.views_width, packed + p.w_off[po + 4 + 2 * j], in, 0, j == 0 ? p.width : p.views_width,
-                            spare, j == 0 ? p.width : p.views_width, false, j == 0 ? nullptr : acts + p.c_hv[j - 1]);
-            if (rc != SNERF_OK) return rc;
-            std::swap(dzv, spare);
-        }
-        float* dfeature = dzv;          // (N, width)
-        float* dlast = spare;
-        rc = weight_grad(dfeature, p.width, p.width, h_last, p.width, grads[po + 2], grads[po + 3]);
-        if (rc != SNERF_OK) return rc;
-        rc = input_grad(dfeature, p.width, p.width, packed + p.w_off[po + 2], p.width, 0, p.width, dlast, p.width, false, nullptr);
-        if (rc != SNERF_OK) return rc;
-        dh = dlast; other = dfeature;
-    }
-    // density head (and the view-independent colour rows): dW_out, and its contribution to d H_D-1, then the ReLU gate
-    rc = weight_grad(dout, 4, p.pts_out_rows, h_last, p.width, grads[po], grads[po + 1]);
-    if (rc != SNERF_OK) return rc;
-    rc = input_grad(dout, 4, p.pts_out_rows, packed + p.w_off[po], p.width, 0, p.width, dh, p.width, p.view_dep, h_last);
-    if (rc != SNERF_OK) return rc;
-    // trunk, last layer first: dh holds dZ_l
-    for (int l = p.depth - 1; l >= 0; --l) {
-        const int in = p.layer_in_dim(l);
-        rc = weight_grad(dh, p.width, p.width, acts + p.layer_in_col(l), in, grads[2 * l], grads[2 * l + 1]);
-        if (rc != SNERF_OK) return rc;
-        if (l == 0) break;
-        const int col0 = in - p.width;       // the skip layer's input is [encoding | H_l-1]: only the H columns carry on
-        rc = input_grad(dh, p.width, p.width, packed + p.w_off[2 * l], in, col0, p.width, other, p.width, false, acts + p.c_h[l - 1]);
-        if (rc != SNERF_OK) return rc;
-        std::swap(dh, other);
-    }
-    return SNERF_OK;
+    auto call = bf16 ? generic_backward_bf16 : backward_walk<F32Operands>;
+    return call(p, packed, acts, sigma, rgb, d_sigma, d_rgb, total, workspace, grads, accumulate, s);
 }
 
 }  // namespace snerf

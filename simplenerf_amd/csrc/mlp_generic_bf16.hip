@@ -1,9 +1,9 @@
 // The layered MLP path (mlp_generic.hip) on bf16 operands: hip_precision 'bf16' and 'bf16s8' for every shape the fused kernels are
-// not built for.  Same design as the fp32 path -- activations in memory, one strided GEMM per Linear layer, fixed-order reductions --
-// with the mode semantics of the fused bf16 kernels: fp32 master weights rounded to bf16 as they are staged (the packed
-// buffer is the fp32 path's, unchanged), encodings, hidden activations and layer gradients dZ held as bf16, fp32 accumulation, and
-// the heads, sigma, rgb, the density noise, the bias sums and the split-K partial sums in fp32.  'bf16s8' is 'bf16' here: the fp8
-// saved trunk exists for the fused 256-wide kernels only.
+// not built for.  The same layer walk as the fp32 path (mlp_generic_walk.h); this file is the bf16 operand format it is instantiated
+// with, with the mode semantics of the fused bf16 kernels: fp32 master weights rounded to bf16 as they are staged (the
+// packed buffer is the fp32 path's, unchanged), encodings, hidden activations and layer gradients dZ held as bf16, fp32
+// accumulation, and the heads, sigma, rgb, the density noise, the bias sums and the split-K partial sums in fp32.  'bf16s8' is
+// 'bf16' here: the fp8 saved trunk exists for the fused 256-wide kernels only.
 //
 // Activation matrix: one row of bf16 per sample, the fp32 path's blocks in the same order but each starting at a multiple of EIGHT
 // elements (16 bytes: the GEMM stages 8 bf16 per load), followed by an fp32 [N][8] block for the two heads' outputs (pts_output in
@@ -18,15 +18,14 @@
 // thread and group: one 16-byte load (bf16) or two (fp32, rounded to bf16 with v_cvt_pk_bf16_f32 as they are stored) where
 // strides and addresses allow it, element by element otherwise (the ragged 63-, 575- and 539-wide products of the fp32 weights).
 #include <algorithm>
-#include <type_traits>
 
 #include "mlp_device.h"
 #include "mlp_generic.h"
 #include "mlp_generic_kernels.h"
+#include "mlp_generic_walk.h"
 
 namespace {
 
-using snerf::GenericPlan;
 typedef unsigned short bf16_t;                                    // bf16 bits in memory
 typedef __bf16 gbf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 gbf16x2 __attribute__((ext_vector_type(2)));
@@ -336,20 +335,13 @@ __global__ void __launch_bounds__(512) colsum8_bf16_kernel(const bf16_t* __restr
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-bool aligned16(const void* ptr) { return reinterpret_cast<uintptr_t>(ptr) % 16 == 0; }
-
 template <int LA, int LB, typename TA, typename TB, typename TC>
 int launch16(const GemmBf16Args& g, int splits, hipStream_t s) {
     if (g.M <= 0 || g.N <= 0) return SNERF_OK;
-    // (each output element is one fp32 chain over k in order whatever the tile: the tile only decides which workgroup computes it)
-    const long long large_tiles = (long long)((g.N + 127) / 128) * ((g.M + 127) / 128) * (splits > 0 ? splits : 1);
-    if (g.M >= 128 && g.N >= 128 && large_tiles >= 512) {
-        const dim3 grid((g.N + 127) / 128, (g.M + 127) / 128, splits > 0 ? splits : 1);
-        hipLaunchKernelGGL((gemm_bf16_kernel<128, 128, LA, LB, TA, TB, TC>), grid, dim3(256), 0, s, g);
-    } else {
-        const dim3 grid((g.N + 63) / 64, (g.M + 63) / 64, splits > 0 ? splits : 1);
-        hipLaunchKernelGGL((gemm_bf16_kernel<64, 64, LA, LB, TA, TB, TC>), grid, dim3(256), 0, s, g);
-    }
+    int tile = 0;
+    const dim3 grid = gemm_grid(g.M, g.N, splits, &tile);
+    if (tile == 128) hipLaunchKernelGGL((gemm_bf16_kernel<128, 128, LA, LB, TA, TB, TC>), grid, dim3(256), 0, s, g);
+    else hipLaunchKernelGGL((gemm_bf16_kernel<64, 64, LA, LB, TA, TB, TC>), grid, dim3(256), 0, s, g);
     return snerf::check_launch("mlp_generic_bf16(gemm)");
 }
 
@@ -360,223 +352,83 @@ int launch16(const GemmBf16Args& g, int splits, hipStream_t s) {
 // operands (the weights, the head gradients) get no such slack: whole groups only.
 bool vec_bf16(const void* base, long long stride) { return aligned16(base) && stride % 8 == 0; }
 bool vec_f32(const void* base, long long stride, long long extent) { return aligned16(base) && stride % 4 == 0 && extent % 8 == 0; }
+template <typename T> bool vec(const T* base, long long stride, long long extent) {
+    return sizeof(T) == 2 ? vec_bf16(base, stride) : vec_f32(base, stride, extent);
+}
 
-long long round8(long long v) { return (v + 7) / 8 * 8; }
+// The bf16 operand format of the layer walk (row and workspace: top of this file).  A dZ is bf16 (a layer's) or fp32 (a head's): TA.
+struct Bf16Operands {
+    using Act = bf16_t;
+    static constexpr const char* kName = "mlp_generic_bf16";
+    static constexpr int kAlign = 8;
+    static constexpr bool kHeadsInRow = false;
+    static long long ld(long long width) { return (width + 7) / 8 * 8; }
+    static long long floats(long long elems) { return (elems + 7) / 8 * 4; }      // whole 16-byte groups
 
-// The bf16 activation row: the fp32 path's blocks in its order, each at a multiple of eight elements; no head columns (the heads go
-// to the fp32 block after the matrix).  Columns and `row` in bf16 elements.
-GenericPlan bf16_layout(const GenericPlan& p) {
-    GenericPlan q = p;
-    int c = 0;
-    auto eight = [&]() { c = (c + 7) / 8 * 8; };
-    q.c_pe = c; c += p.pe_full;
-    eight(); q.c_pev = c; c += p.views_pe;
-    q.c_x5 = -1;
-    for (int l = 0; l < p.depth; ++l) {
-        eight();
-        if (l == 4 && p.depth > 5) { q.c_x5 = c; c += p.pts_in; }      // [encoding | H_4] as ONE block: H_4 follows directly
-        q.c_h[l] = c; c += p.width;
+    // Y[rows, out] = act(X[rows, in] . W[out, in]^T + b), X bf16 columns of the activation matrix, Y bf16 columns or the fp32 heads block
+    template <typename TC>
+    static int linear(const bf16_t* x, long long x_rs, TC* y, long long y_rs, long long rows, int in, int out, const float* w,
+                      const float* b, bool relu, hipStream_t s) {
+        GemmBf16Args g = {};
+        g.A = x; g.a_rs = x_rs; g.a_cs = 1;
+        g.B = w; g.b_rs = 1; g.b_cs = in;
+        g.C = y; g.c_rs = y_rs;
+        g.bias = b; g.M = (int)rows; g.N = out; g.K = in; g.relu = relu ? 1 : 0;
+        g.a_vec = vec_bf16(x, x_rs);
+        g.b_vec = vec_f32(w, in, in);
+        return launch16<0, 0, bf16_t, float, TC>(g, 0, s);
     }
-    eight(); q.c_v0 = c; if (p.view_dep) c += p.views_in;
-    for (int j = 0; j < p.views_depth; ++j) { eight(); q.c_hv[j] = c; c += p.views_width; }
-    eight();
-    q.c_out = q.c_vout = -1;
-    q.row = c;
-    return q;
-}
-
-// floats of the bf16 matrix of `total` rows (rounded up to whole 16-byte groups); the fp32 heads block follows it
-long long matrix_floats(const GenericPlan& q, long long total) { return (total * q.row / 2 + 3) / 4 * 4; }
-
-// Y[rows, out] = act(X[rows, in] . W[out, in]^T + b), X bf16 columns of the activation matrix, Y bf16 columns or the fp32 heads block
-template <typename TC>
-int linear16(const bf16_t* x, long long x_rs, TC* y, long long y_rs, long long rows, int in, int out, const float* w, const float* b,
-             bool relu, hipStream_t s) {
-    GemmBf16Args g = {};
-    g.A = x; g.a_rs = x_rs; g.a_cs = 1;
-    g.B = w; g.b_rs = 1; g.b_cs = in;
-    g.C = y; g.c_rs = y_rs;
-    g.bias = b; g.M = (int)rows; g.N = out; g.K = in; g.relu = relu ? 1 : 0;
-    g.a_vec = vec_bf16(x, x_rs);
-    g.b_vec = vec_f32(w, in, in);
-    return launch16<0, 0, bf16_t, float, TC>(g, 0, s);
-}
+    template <typename TA>
+    static int input_grad(const TA* dz, long long dz_ld, int out, const float* w, int w_ld, int cols, bf16_t* dx, long long dx_ld,
+                          bool add, const bf16_t* gate, long long gate_rs, long long rows, hipStream_t s) {
+        GemmBf16Args g = {};
+        g.A = dz; g.a_rs = dz_ld; g.a_cs = 1;
+        g.B = w; g.b_rs = w_ld; g.b_cs = 1;
+        g.C = dx; g.c_rs = dx_ld;
+        g.M = (int)rows; g.N = cols; g.K = out; g.accumulate = add ? 1 : 0;
+        g.mask = gate; g.mask_rs = gate_rs;
+        g.a_vec = vec(dz, dz_ld, out);
+        g.b_vec = vec_f32(w, w_ld, cols);
+        return launch16<0, 1, TA, float, bf16_t>(g, 0, s);
+    }
+    template <typename TA>
+    static int wgrad_gemm(const TA* dz, long long dz_ld, int out, const bf16_t* x, long long x_rs, int in, long long total, int splits,
+                          long long k_chunk, float* partial, hipStream_t s) {
+        GemmBf16Args g = {};
+        g.A = dz; g.a_rs = 1; g.a_cs = dz_ld;           // A(m = out feature, k = sample) = dZ[k][m]
+        g.B = x; g.b_rs = x_rs; g.b_cs = 1;             // B(k = sample, n = in feature)
+        g.C = partial; g.c_rs = in;
+        g.M = out; g.N = in; g.K = (int)total; g.k_chunk = k_chunk; g.split_stride = (long long)out * in;
+        g.a_vec = vec(dz, dz_ld, out);
+        g.b_vec = vec_bf16(x, x_rs);
+        return launch16<1, 1, TA, bf16_t, float>(g, splits, s);
+    }
+    static int colsum(const bf16_t* dz, long long dz_ld, int out, long long total, int bsplits, long long b_chunk, float* bpart,
+                      hipStream_t s) {
+        if (dz_ld % 8 != 0 || !aligned16(dz)) return snerf::fail(SNERF_E_INVALID, "mlp_backward(layered, bf16): workspace not 16-byte aligned");
+        hipLaunchKernelGGL(colsum8_bf16_kernel, dim3((out + 511) / 512, bsplits), dim3(512), 0, s, dz, dz_ld, total, out, b_chunk, bpart);
+        return SNERF_OK;
+    }
+    static int colsum(const float* dz, long long dz_ld, int out, long long total, int bsplits, long long b_chunk, float* bpart, hipStream_t s) {
+        hipLaunchKernelGGL(colsum_kernel, dim3((out + 63) / 64, bsplits), dim3(256), 0, s, dz, dz_ld, total, out, b_chunk, bpart);
+        return SNERF_OK;
+    }
+};
 
 }  // namespace
 
 namespace snerf {
 
-int generic_forward_rows_bf16(const GenericPlan& p, const float* packed, const float* origins, const float* dirs, const float* view_dirs,
-                              const float* depths, long long first, long long total, int samples, const float* noise, float* sigma,
-                              float* rgb, float* acts_floats, hipStream_t s) {
-    const GenericPlan q = bf16_layout(p);
-    const long long heads_at = matrix_floats(q, total);
-    if (heads_at + 8 * total > (long long)generic_saved_floats(p, total))
-        return fail(SNERF_E_UNSUPPORTED, "mlp_forward(layered, bf16): activation row of %lld bf16 + 8 fp32 exceeds %lld floats", q.row, p.row);
-    bf16_t* acts = reinterpret_cast<bf16_t*>(acts_floats);
-    float* heads = acts_floats + heads_at;
-    EncodeArgs e = {};
-    e.origins = origins + (first / samples) * 3; e.dirs = dirs + (first / samples) * 3;
-    e.view_dirs = view_dirs ? view_dirs + (first / samples) * 3 : nullptr;
-    // (the chunk starts at a ray boundary: the caller cuts whole rays)
-    e.depths = depths + first; e.acts = acts; e.row = q.row; e.total = total; e.samples = samples;
-    e.points_degree = p.points_degree; e.views_degree = p.views_degree; e.pe_full = p.pe_full; e.pts_in = p.pts_in;
-    e.views_pe = p.view_dep ? p.views_pe : 0;
-    e.c_pe = q.c_pe; e.c_pev = q.c_pev; e.c_x5 = q.c_x5; e.c_v0_extra = p.view_dep && p.extra > 0 ? q.c_v0 + p.width : -1;
-    e.c_v0_views = p.view_dep ? q.c_v0 + p.width + p.extra : -1;
-    hipLaunchKernelGGL(encode_kernel<bf16_t>, dim3(stride_grid(total * (p.pe_full + (p.view_dep ? p.views_pe : 0)), 256)), dim3(256), 0, s, e);
-    int rc = check_launch("mlp_generic_bf16(encode)");
-    if (rc != SNERF_OK) return rc;
-    for (int l = 0; l < p.depth; ++l) {
-        rc = linear16<bf16_t>(acts + q.layer_in_col(l), q.row, acts + q.c_h[l], q.row, total, p.layer_in_dim(l), p.width,
-                              packed + p.w_off[2 * l], packed + p.w_off[2 * l + 1], true, s);
-        if (rc != SNERF_OK) return rc;
-    }
-    const int po = 2 * p.depth;
-    rc = linear16<float>(acts + q.c_h[p.depth - 1], q.row, heads, 8, total, p.width, p.pts_out_rows, packed + p.w_off[po],
-                         packed + p.w_off[po + 1], false, s);
-    if (rc != SNERF_OK) return rc;
-    if (p.view_dep) {
-        rc = linear16<bf16_t>(acts + q.c_h[p.depth - 1], q.row, acts + q.c_v0, q.row, total, p.width, p.width, packed + p.w_off[po + 2],
-                              packed + p.w_off[po + 3], false, s);                                   // feature: no activation (:683)
-        if (rc != SNERF_OK) return rc;
-        for (int j = 0; j < p.views_depth; ++j) {
-            rc = linear16<bf16_t>(acts + (j == 0 ? q.c_v0 : q.c_hv[j - 1]), q.row, acts + q.c_hv[j], q.row, total,
-                                  j == 0 ? p.views_in : p.views_width, p.views_width, packed + p.w_off[po + 4 + 2 * j],
-                                  packed + p.w_off[po + 5 + 2 * j], true, s);
-            if (rc != SNERF_OK) return rc;
-        }
-        const int pv = po + 4 + 2 * p.views_depth;
-        rc = linear16<float>(acts + q.c_hv[p.views_depth - 1], q.row, heads + 4, 8, total, p.views_width, 3, packed + p.w_off[pv],
-                             packed + p.w_off[pv + 1], false, s);
-        if (rc != SNERF_OK) return rc;
-    }
-    hipLaunchKernelGGL(heads_kernel, dim3(stride_grid(total, 256)), dim3(256), 0, s, heads, 8LL, 0, 4, p.view_dep ? 1 : 0,
-                       noise ? noise + first : nullptr, total, sigma + first, rgb + first * 3);
-    return check_launch("mlp_generic_bf16(heads)");
+int generic_forward_bf16(const GenericPlan& p, const float* packed, const float* origins, const float* dirs, const float* view_dirs,
+                         const float* depths, long long num_rays, int num_samples, const float* noise, float* sigma, float* rgb,
+                         float* saved_acts, hipStream_t s) {
+    return forward_call<Bf16Operands>(p, packed, origins, dirs, view_dirs, depths, num_rays, num_samples, noise, sigma, rgb, saved_acts, s);
 }
 
-// workspace: dZ ping-pong (2 x N x widest rounded up to 8, bf16) | d heads (2 x N x 4, fp32) | split-K partial sums (fp32)
-int generic_backward_bf16(const GenericPlan& p, const float* packed, const float* acts_floats, const float* sigma, const float* rgb,
+int generic_backward_bf16(const GenericPlan& p, const float* packed, const float* acts, const float* sigma, const float* rgb,
                           const float* d_sigma, const float* d_rgb, long long total, float* workspace, float* const* grads,
                           int accumulate, hipStream_t s) {
-    const GenericPlan q = bf16_layout(p);
-    const bf16_t* acts = reinterpret_cast<const bf16_t*>(acts_floats);
-    const long long widest = std::max({p.width, p.views_width, p.views_in, p.pts_in + p.width});
-    const long long biggest = std::max({(long long)p.width * (p.pts_in + p.width), (long long)p.views_width * p.views_in,
-                                        (long long)p.views_width * p.views_width, (long long)p.width * p.width});
-    const long long ld_t = round8(p.width), ld_v = round8(p.views_width);      // row strides of the dZ buffers
-    const long long dz_floats = (total * round8(widest) / 2 + 3) / 4 * 4;
-    const int splits = generic_wgrad_splits(total);
-    if (2 * dz_floats + 8 * total + (long long)splits * (biggest + widest) > (long long)generic_backward_workspace_floats(p, total))
-        return fail(SNERF_E_UNSUPPORTED, "mlp_backward(layered, bf16): workspace layout exceeds the reported size");
-    bf16_t* ping = reinterpret_cast<bf16_t*>(workspace);
-    bf16_t* pong = reinterpret_cast<bf16_t*>(workspace + dz_floats);
-    float* dout = workspace + 2 * dz_floats;
-    float* dvout = dout + 4 * total;
-    float* partial = dvout + 4 * total;
-    const long long k_chunk = (total + splits - 1) / splits;
-
-    hipLaunchKernelGGL(heads_backward_kernel, dim3(stride_grid(total, 256)), dim3(256), 0, s, sigma, rgb, d_sigma, d_rgb, total,
-                       p.view_dep ? 1 : 0, dout, dvout);
-    int rc = check_launch("mlp_generic_bf16(heads backward)");
-    if (rc != SNERF_OK) return rc;
-
-    // dW = dZ^T . X (split over the samples, fixed-order reduction), db = column sums of dZ; dZ bf16 (a layer) or fp32 (a head)
-    auto weight_grad = [&](auto dz, long long dz_ld, int out, const bf16_t* x, int in, float* gw, float* gb) -> int {
-        using TA = std::remove_const_t<std::remove_pointer_t<decltype(dz)>>;
-        GemmBf16Args g = {};
-        g.A = dz; g.a_rs = 1; g.a_cs = dz_ld;           // A(m = out feature, k = sample) = dZ[k][m]
-        g.B = x; g.b_rs = q.row; g.b_cs = 1;            // B(k = sample, n = in feature)
-        g.C = partial; g.c_rs = in;
-        g.M = out; g.N = in; g.K = (int)total; g.k_chunk = k_chunk; g.split_stride = (long long)out * in;
-        g.a_vec = sizeof(TA) == 2 ? vec_bf16(dz, dz_ld) : vec_f32(dz, dz_ld, out);
-        g.b_vec = vec_bf16(x, q.row);
-        int st = launch16<1, 1, TA, bf16_t, float>(g, splits, s);
-        if (st != SNERF_OK) return st;
-        hipLaunchKernelGGL(reduce_splits_kernel, dim3(stride_grid((long long)out * in, 256)), dim3(256), 0, s, partial,
-                           (long long)out * in, splits, (long long)out * in, gw, accumulate);
-        st = check_launch("mlp_generic_bf16(reduce)");
-        if (st != SNERF_OK) return st;
-        // (the weight partial sums are folded: their area takes the bias partial rows -- room for splits x in rows of `out`)
-        const int bsplits = in >= 4 ? splits * 4 : splits;
-        const long long b_chunk = (total + bsplits - 1) / bsplits;
-        float* bpart = partial;
-        if constexpr (sizeof(TA) == 2) {
-            if (dz_ld % 8 != 0 || !aligned16(dz)) return fail(SNERF_E_INVALID, "mlp_backward(layered, bf16): workspace not 16-byte aligned");
-            hipLaunchKernelGGL(colsum8_bf16_kernel, dim3((out + 511) / 512, bsplits), dim3(512), 0, s, dz, dz_ld, total, out, b_chunk, bpart);
-        } else {
-            hipLaunchKernelGGL(colsum_kernel, dim3((out + 63) / 64, bsplits), dim3(256), 0, s, dz, dz_ld, total, out, b_chunk, bpart);
-        }
-        st = check_launch("mlp_generic_bf16(bias sums)");
-        if (st != SNERF_OK) return st;
-        hipLaunchKernelGGL(reduce_splits_kernel, dim3(1), dim3(256), 0, s, bpart, (long long)out, bsplits, (long long)out, gb, accumulate);
-        return check_launch("mlp_generic_bf16(reduce bias)");
-    };
-    // dX[:, cols] (+)= dZ . W[:, col0 : col0 + cols], then gated by the ReLU of the layer that produced X; dX bf16
-    auto input_grad = [&](auto dz, long long dz_ld, int out, const float* w, int w_ld, int col0, int cols, bf16_t* dx, long long dx_ld,
-                          bool add, const bf16_t* gate) -> int {
-        using TA = std::remove_const_t<std::remove_pointer_t<decltype(dz)>>;
-        GemmBf16Args g = {};
-        g.A = dz; g.a_rs = dz_ld; g.a_cs = 1;
-        g.B = w + col0; g.b_rs = w_ld; g.b_cs = 1;
-        g.C = dx; g.c_rs = dx_ld;
-        g.M = (int)total; g.N = cols; g.K = out; g.accumulate = add ? 1 : 0;
-        g.mask = gate; g.mask_rs = q.row;
-        g.a_vec = sizeof(TA) == 2 ? vec_bf16(dz, dz_ld) : vec_f32(dz, dz_ld, out);
-        g.b_vec = vec_f32(w + col0, w_ld, cols);
-        return launch16<0, 1, TA, float, bf16_t>(g, 0, s);
-    };
-
-    const int po = 2 * p.depth;
-    bf16_t* dh = ping;        // gradient of the trunk's last activation H_D-1, then dZ of each trunk layer in turn (row stride ld_t)
-    bf16_t* other = pong;
-    const bf16_t* h_last = acts + q.c_h[p.depth - 1];
-    if (p.view_dep) {
-        const int pv = po + 4 + 2 * p.views_depth;
-        // views head and views layers, last first
-        rc = weight_grad((const float*)dvout, 4, 3, acts + q.c_hv[p.views_depth - 1], p.views_width, grads[pv], grads[pv + 1]);
-        if (rc != SNERF_OK) return rc;
-        rc = input_grad((const float*)dvout, 4, 3, packed + p.w_off[pv], p.views_width, 0, p.views_width, other, ld_v, false,
-                        acts + q.c_hv[p.views_depth - 1]);
-        if (rc != SNERF_OK) return rc;
-        bf16_t* dzv = other; bf16_t* spare = dh;
-        for (int j = p.views_depth - 1; j >= 0; --j) {
-            const int in = j == 0 ? p.views_in : p.views_width;
-            const bf16_t* x = acts + (j == 0 ? q.c_v0 : q.c_hv[j - 1]);
-            rc = weight_grad((const bf16_t*)dzv, ld_v, p.views_width, x, in, grads[po + 4 + 2 * j], grads[po + 5 + 2 * j]);
-            if (rc != SNERF_OK) return rc;
-            // j > 0: d HV_j-1, gated by its ReLU; j == 0: d feature = the first `width` columns of the views input (no activation)
-            rc = input_grad((const bf16_t*)dzv, ld_v, p.views_width, packed + p.w_off[po + 4 + 2 * j], in, 0,
-                            j == 0 ? p.width : p.views_width, spare, j == 0 ? ld_t : ld_v, false, j == 0 ? nullptr : acts + q.c_hv[j - 1]);
-            if (rc != SNERF_OK) return rc;
-            std::swap(dzv, spare);
-        }
-        bf16_t* dfeature = dzv;          // (N, width), row stride ld_t
-        bf16_t* dlast = spare;
-        rc = weight_grad((const bf16_t*)dfeature, ld_t, p.width, h_last, p.width, grads[po + 2], grads[po + 3]);
-        if (rc != SNERF_OK) return rc;
-        rc = input_grad((const bf16_t*)dfeature, ld_t, p.width, packed + p.w_off[po + 2], p.width, 0, p.width, dlast, ld_t, false, nullptr);
-        if (rc != SNERF_OK) return rc;
-        dh = dlast; other = dfeature;
-    }
-    // density head (and the view-independent colour rows): dW_out, and its contribution to d H_D-1, then the ReLU gate
-    rc = weight_grad((const float*)dout, 4, p.pts_out_rows, h_last, p.width, grads[po], grads[po + 1]);
-    if (rc != SNERF_OK) return rc;
-    rc = input_grad((const float*)dout, 4, p.pts_out_rows, packed + p.w_off[po], p.width, 0, p.width, dh, ld_t, p.view_dep, h_last);
-    if (rc != SNERF_OK) return rc;
-    // trunk, last layer first: dh holds dZ_l
-    for (int l = p.depth - 1; l >= 0; --l) {
-        const int in = p.layer_in_dim(l);
-        rc = weight_grad((const bf16_t*)dh, ld_t, p.width, acts + q.layer_in_col(l), in, grads[2 * l], grads[2 * l + 1]);
-        if (rc != SNERF_OK) return rc;
-        if (l == 0) break;
-        const int col0 = in - p.width;       // the skip layer's input is [encoding | H_l-1]: only the H columns carry on
-        rc = input_grad((const bf16_t*)dh, ld_t, p.width, packed + p.w_off[2 * l], in, col0, p.width, other, ld_t, false, acts + q.c_h[l - 1]);
-        if (rc != SNERF_OK) return rc;
-        std::swap(dh, other);
-    }
-    return SNERF_OK;
+    return backward_walk<Bf16Operands>(p, packed, acts, sigma, rgb, d_sigma, d_rgb, total, workspace, grads, accumulate, s);
 }
 
 }  // namespace snerf
