@@ -32,7 +32,7 @@ enum snerf_status {
 
 /* ABI version of this header; bumped on any signature change (new enum values such as SNERF_PRECISION_F16 extend a
  * version without changing it: older callers never pass them). */
-#define SNERF_ABI_VERSION 9
+#define SNERF_ABI_VERSION 10
 /* Threads (no ABI change): every entry point may be called from several host threads at once -- on different devices, on
  * different streams of one device, and on the SAME stream (torch.nn.DataParallel with a repeated device id runs its replicas in
  * parallel threads that enqueue on one stream).  The host-side state the library keeps is guarded: the side streams and fork /

@@ -26,7 +26,10 @@ extern "C" {
  *                 denominator_mask);  0 when the denominator count is 0 (the reference's `if numel() > 0 else 0`)
  *   numerator_mask == denominator_mask for the plain masked MSE; the patch-consistency depth terms average over all
  *   pixel rays but only count the rays the decision mask keeps (the reference zeroes the others, then takes the mean).
- *   `target` never receives a gradient (the reference detaches it or it is data).
+ *   `target` receives no gradient (the reference detaches it or it is data) unless the term names a `d_target`
+ *   buffer: the plain consistency losses (src/loss_functions/PointsAugmentationDepthLoss01.py:70-74,
+ *   ViewsAugmentationDepthLoss01, CoarseFineConsistencyLoss01.py:39-40) differentiate both operands.  Such a term is
+ *   still ONE term, counted once in its loss's value.
  */
 #define SNERF_LOSS_MAX_TERMS 16
 #define SNERF_LOSS_MAX_GROUPS 16
@@ -41,6 +44,10 @@ typedef struct snerf_loss_term {
     int group;                             /* which loss (LossComputer entry) the term belongs to, 0 <= group < num_groups */
     int accumulate;                        /* backward only: 1 = add to d_pred (an earlier term of the table wrote it) */
     float weight;                          /* the loss weight of LossComputer.get_loss_weight for this iteration */
+    float* d_target;                       /* backward only: device (num_rays, channels) gradient buffer of `target`, or NULL =
+                                              `target` receives no gradient (ABI 10; appended, so a zero-initialised tail
+                                              keeps the one-sided behaviour) */
+    int accumulate_target;                 /* backward only: 1 = add to d_target (an earlier term of the table wrote it) */
 } snerf_loss_term;
 
 /* Bytes of device scratch snerf_loss_forward needs (partial sums + a completion counter that must be zero on first
@@ -56,7 +63,10 @@ int snerf_loss_forward(const snerf_loss_term* terms, int num_terms, int num_grou
 /* upstream  device (num_terms + num_groups + 1): gradient of the caller's scalar with respect to `values` (all zero
  *           except a 1 at [T+G] when the caller back-propagates TotalLoss).
  * Writes d_pred of every term:  (upstream[t] + upstream[T+group] + upstream[T+G]*weight) * scale * (pred - target)
- * on the numerator-masked rays, 0 elsewhere; terms with accumulate=1 add to what an earlier term wrote. */
+ * on the numerator-masked rays, 0 elsewhere; terms with accumulate=1 add to what an earlier term wrote.  A term with a
+ * d_target writes there (accumulate_target=1: adds) the exact negation of that value on the same rays, 0 elsewhere.  One
+ * buffer may be d_pred of one term and d_target of another (same channels): a thread owns a ray of every term and adds in
+ * table order, so the sum is race-free and deterministic. */
 int snerf_loss_backward(const snerf_loss_term* terms, int num_terms, int num_groups, long long num_rays,
                         const float* scales, const float* upstream, snerf_stream_t stream);
 
@@ -130,6 +140,16 @@ int snerf_assemble_batch(const long long* indices, long long num_rays, long long
                          const float* sparse_depths, const float* sparse_errors, const float* sparse_depths_ndc, int ndc,
                          float near, float far, float near_ndc, float far_ndc, long long first_pixel_row,
                          long long first_sparse_row, const snerf_batch* out, snerf_stream_t stream);
+
+/* B1b  dense-depth columns of the batch (ABI 10).  Replaces load_dense_depth_cached_batch (DataPreprocessor01.py:704-722):
+ * the pixel-ray rows (the first num_pixel_rays of `indices`, the buffer snerf_assemble_batch reads -- inside a captured
+ * iteration the one snerf_shuffled_indices_at filled) gather the per-pixel tables at their index, every other row, and a
+ * row whose index lies outside [0, num_pixels), holds the loader's -1.
+ *   depths, weights, depths_ndc   device (num_pixels = num_views*height*width) tables; each may be NULL together with its
+ *   values, values_weights, values_ndc   device (n,1) output.  Enqueues one launch; allocates and synchronises nothing. */
+int snerf_gather_dense_depth(const long long* indices, long long num_rays, long long num_pixel_rays, long long num_pixels,
+                             const float* depths, const float* weights, const float* depths_ndc, float* values,
+                             float* values_weights, float* values_ndc, snerf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * B2  shuffled index stream.  Replaces the host-side index list of generate_indices / select_batch_indices (:252-270,

@@ -12,7 +12,7 @@ from ctypes import (POINTER, c_char_p, c_double, c_float, c_int, c_longlong, c_s
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libsimplenerf_hip.so')
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 ITERATION_WORDS = 8      # struct snerf_iteration as 64-bit words (include/simplenerf_train.h)
@@ -28,7 +28,8 @@ class MlpDesc(ctypes.Structure):
 class LossTerm(ctypes.Structure):
     """struct snerf_loss_term"""
     _fields_ = [('pred', c_void_p), ('target', c_void_p), ('numerator_mask', c_void_p), ('denominator_mask', c_void_p),
-                ('d_pred', c_void_p), ('channels', c_int), ('group', c_int), ('accumulate', c_int), ('weight', c_float)]
+                ('d_pred', c_void_p), ('channels', c_int), ('group', c_int), ('accumulate', c_int), ('weight', c_float),
+                ('d_target', c_void_p), ('accumulate_target', c_int)]
 
 
 class Batch(ctypes.Structure):
@@ -135,6 +136,7 @@ SIGNATURES = {
     'snerf_camera_table': (c_int, [_FP, _FP, c_int, c_int, c_int, _FP, c_void_p]),
     'snerf_assemble_batch': (c_int, [c_void_p, c_longlong, c_longlong, _FP, c_int, c_int, c_int, _FP, _FP, _FP, _FP, c_int,
                                      c_float, c_float, c_float, c_float, c_longlong, c_longlong, POINTER(Batch), c_void_p]),
+    'snerf_gather_dense_depth': (c_int, [c_void_p, c_longlong, c_longlong, c_longlong, _FP, _FP, _FP, _FP, _FP, _FP, c_void_p]),
     'snerf_shuffled_indices': (c_int, [c_ulonglong, c_ulonglong, c_longlong, c_longlong, c_longlong, c_void_p, c_int,
                                        c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'snerf_random_uniform': (c_int, [c_ulonglong, c_uint, c_longlong, c_void_p, c_longlong, c_int, _FP, c_void_p]),

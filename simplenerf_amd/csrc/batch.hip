@@ -86,6 +86,22 @@ __global__ void __launch_bounds__(256) assemble_batch_kernel(AssembleArgs a) {
     }
 }
 
+// B1b: the dense-depth columns.  Row i < num_pixel_rays with an index inside the tables gathers, every other row keeps -1.
+__global__ void __launch_bounds__(256) gather_dense_depth_kernel(const long long* __restrict__ indices, long long num_rays,
+                                                                 long long num_pixel_rays, long long num_pixels,
+                                                                 const float* __restrict__ depths, const float* __restrict__ weights,
+                                                                 const float* __restrict__ depths_ndc, float* __restrict__ values,
+                                                                 float* __restrict__ values_weights, float* __restrict__ values_ndc) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < num_rays; i += stride) {
+        const long long idx = indices[i];
+        const bool take = i < num_pixel_rays && idx >= 0 && idx < num_pixels;
+        if (values) values[i] = take ? depths[idx] : -1.0f;
+        if (values_weights) values_weights[i] = take ? weights[idx] : -1.0f;
+        if (values_ndc) values_ndc[i] = take ? depths_ndc[idx] : -1.0f;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int kFeistelRounds = 8;
 
@@ -254,6 +270,24 @@ extern "C" int snerf_assemble_batch(const long long* indices, long long num_rays
                    first_pixel_row, first_sparse_row, *out};
     hipLaunchKernelGGL(assemble_batch_kernel, dim3(snerf::stride_grid(num_rays, 256)), dim3(256), 0, (hipStream_t)stream, a);
     return snerf::check_launch("assemble_batch");
+}
+
+extern "C" int snerf_gather_dense_depth(const long long* indices, long long num_rays, long long num_pixel_rays,
+                                        long long num_pixels, const float* depths, const float* weights,
+                                        const float* depths_ndc, float* values, float* values_weights, float* values_ndc,
+                                        snerf_stream_t stream) {
+    SNERF_REQUIRE(indices, "gather_dense_depth: NULL indices");
+    SNERF_REQUIRE(num_rays >= 0 && num_pixel_rays >= 0 && num_pixel_rays <= num_rays,
+                  "gather_dense_depth: %lld pixel rays of %lld rows", num_pixel_rays, num_rays);
+    SNERF_REQUIRE(num_pixels >= 1, "gather_dense_depth: %lld table entries", num_pixels);
+    SNERF_REQUIRE(values || values_weights || values_ndc, "gather_dense_depth: no output");
+    SNERF_REQUIRE((!values || depths) && (!values_weights || weights) && (!values_ndc || depths_ndc),
+                  "gather_dense_depth: an output is wanted whose table is NULL");
+    if (num_rays == 0) return SNERF_OK;
+    hipLaunchKernelGGL(gather_dense_depth_kernel, dim3(snerf::stride_grid(num_rays, 256)), dim3(256), 0, (hipStream_t)stream,
+                       indices, num_rays, num_pixel_rays, num_pixels, depths, weights, depths_ndc, values, values_weights,
+                       values_ndc);
+    return snerf::check_launch("gather_dense_depth");
 }
 
 static int shuffled_indices_impl(unsigned long long seed, unsigned long long epoch, long long first, long long count,

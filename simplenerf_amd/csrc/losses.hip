@@ -17,10 +17,30 @@ constexpr int kMaxGroups = SNERF_LOSS_MAX_GROUPS;
 constexpr int kBlock = 256;
 constexpr int kMaxBlocks = 64;
 
+// A term as the kernels read it: the fields of snerf_loss_term without its backward-only tail (d_target), which only the
+// mirrored backward needs -- it travels in a table of its own, so that a table of one-sided terms costs what it always did.
+struct KernelTerm {
+    const float* pred;
+    const float* target;
+    const unsigned char* numerator_mask;
+    const unsigned char* denominator_mask;
+    float* d_pred;
+    int channels;
+    int group;
+    int accumulate;
+    float weight;
+};
+
 struct TermTable {
-    snerf_loss_term term[kMaxTerms];
+    KernelTerm term[kMaxTerms];
     int num_terms;
     int num_groups;
+};
+
+struct MirrorTable {
+    float* d_target[kMaxTerms];
+    unsigned wanted;       // bit t: term t writes d_target[t]
+    unsigned accumulate;   // bit t: ... by adding to it
 };
 
 struct Workspace {
@@ -35,7 +55,7 @@ __device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
     return v;
 }
 
-__device__ __forceinline__ float squared_error(const snerf_loss_term& t, long long ray) {
+__device__ __forceinline__ float squared_error(const KernelTerm& t, long long ray) {
     if (t.channels == 1) {
         const float e = t.pred[ray] - t.target[ray];
         return e * e;
@@ -68,7 +88,7 @@ __global__ void __launch_bounds__(kBlock) loss_forward_kernel(TermTable table, l
 #pragma unroll
         for (int t = 0; t < kMaxTerms; ++t) {
             if (t < table.num_terms) {
-                const snerf_loss_term& term = table.term[t];
+                const KernelTerm& term = table.term[t];
                 if (!term.denominator_mask || term.denominator_mask[ray]) cnt[t] += 1;
                 if (!term.numerator_mask || term.numerator_mask[ray]) sum[t] += squared_error(term, ray);
             }
@@ -138,28 +158,53 @@ __global__ void __launch_bounds__(kBlock) loss_forward_kernel(TermTable table, l
 }
 
 // Pass 2: every gradient.  A thread owns ray r of every term, so two terms that share a gradient buffer (a depth read
-// by several losses) are summed by the same thread in table order: race-free and deterministic.
-__global__ void __launch_bounds__(kBlock) loss_backward_kernel(TermTable table, long long num_rays,
-                                                               const float* __restrict__ scales,
-                                                               const float* __restrict__ upstream) {
+// by several losses, as pred of one and as the differentiated target of another) are summed by the same thread in table
+// order: race-free and deterministic.  kMirror = false is the backward of a table without a d_target, instruction for
+// instruction what it was before d_target existed; kMirror = true also writes, for the terms of `mirror.wanted`, the exact
+// negation of the value that goes to d_pred.
+template <bool kMirror>
+__device__ __forceinline__ void loss_backward_body(const TermTable& table, const MirrorTable* mirror, long long num_rays,
+                                                   const float* __restrict__ scales, const float* __restrict__ upstream) {
     const int T = table.num_terms, G = table.num_groups;
     const float up_total = upstream[T + G];
     const long long stride = (long long)gridDim.x * kBlock;
     for (long long ray = (long long)blockIdx.x * kBlock + threadIdx.x; ray < num_rays; ray += stride) {
 #pragma unroll 1
         for (int t = 0; t < T; ++t) {
-            const snerf_loss_term& term = table.term[t];
-            if (!term.d_pred) continue;
+            const KernelTerm& term = table.term[t];
+            const bool mirrored = kMirror && ((mirror->wanted >> t) & 1u);
+            if (!term.d_pred && !mirrored) continue;
             const float factor = (upstream[t] + upstream[T + term.group] + up_total * term.weight) * scales[t];
             const bool on = !term.numerator_mask || term.numerator_mask[ray];
             for (int c = 0; c < term.channels; ++c) {
                 const long long i = ray * term.channels + c;
-                float g = on ? factor * (term.pred[i] - term.target[i]) : 0.0f;
-                if (term.accumulate) g += term.d_pred[i];
-                term.d_pred[i] = g;
+                const float own = on ? factor * (term.pred[i] - term.target[i]) : 0.0f;
+                if (term.d_pred) {
+                    float g = own;
+                    if (term.accumulate) g += term.d_pred[i];
+                    term.d_pred[i] = g;
+                }
+                if (mirrored) {
+                    float* d_target = mirror->d_target[t];
+                    float g = on ? -own : 0.0f;
+                    if ((mirror->accumulate >> t) & 1u) g += d_target[i];
+                    d_target[i] = g;
+                }
             }
         }
     }
+}
+
+__global__ void __launch_bounds__(kBlock) loss_backward_kernel(TermTable table, long long num_rays,
+                                                               const float* __restrict__ scales,
+                                                               const float* __restrict__ upstream) {
+    loss_backward_body<false>(table, nullptr, num_rays, scales, upstream);
+}
+
+__global__ void __launch_bounds__(kBlock) loss_backward_mirror_kernel(TermTable table, MirrorTable mirror, long long num_rays,
+                                                                      const float* __restrict__ scales,
+                                                                      const float* __restrict__ upstream) {
+    loss_backward_body<true>(table, &mirror, num_rays, scales, upstream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -292,7 +337,8 @@ __global__ void __launch_bounds__(256) patch_masks_kernel(PatchArgs a) {
     }
 }
 
-int fill_table(const snerf_loss_term* terms, int num_terms, int num_groups, bool backward, TermTable* table) {
+int fill_table(const snerf_loss_term* terms, int num_terms, int num_groups, bool backward, TermTable* table,
+               MirrorTable* mirror = nullptr) {
     SNERF_REQUIRE(terms, "loss: NULL term table");
     SNERF_REQUIRE(num_terms >= 1 && num_terms <= kMaxTerms, "loss: num_terms %d outside [1,%d]", num_terms, kMaxTerms);
     SNERF_REQUIRE(num_groups >= 1 && num_groups <= kMaxGroups, "loss: num_groups %d outside [1,%d]", num_groups, kMaxGroups);
@@ -300,12 +346,28 @@ int fill_table(const snerf_loss_term* terms, int num_terms, int num_groups, bool
         SNERF_REQUIRE(terms[t].pred && terms[t].target, "loss: term %d has a NULL pred/target", t);
         SNERF_REQUIRE(terms[t].channels >= 1 && terms[t].channels <= 4, "loss: term %d channels %d outside [1,4]", t, terms[t].channels);
         SNERF_REQUIRE(terms[t].group >= 0 && terms[t].group < num_groups, "loss: term %d group %d outside [0,%d)", t, terms[t].group, num_groups);
-        if (backward && terms[t].accumulate) {
-            bool earlier = false;
-            for (int s = 0; s < t; ++s) earlier |= terms[s].d_pred == terms[t].d_pred && terms[s].channels == terms[t].channels;
-            SNERF_REQUIRE(earlier, "loss: term %d accumulates into a buffer no earlier term wrote", t);
+        if (backward) {
+            // a buffer written earlier in the table (as d_pred or d_target of a term with the same row layout)
+            auto written = [&](const float* buffer) {
+                bool earlier = false;
+                for (int s = 0; s < t; ++s)
+                    earlier |= terms[s].channels == terms[t].channels && (terms[s].d_pred == buffer || terms[s].d_target == buffer);
+                return earlier;
+            };
+            SNERF_REQUIRE(!terms[t].accumulate || (terms[t].d_pred && written(terms[t].d_pred)),
+                          "loss: term %d accumulates into a buffer no earlier term wrote", t);
+            SNERF_REQUIRE(!terms[t].accumulate_target || (terms[t].d_target && written(terms[t].d_target)),
+                          "loss: term %d accumulates its target gradient into a buffer no earlier term wrote", t);
+            SNERF_REQUIRE(!terms[t].d_target || terms[t].d_target != terms[t].d_pred,
+                          "loss: term %d names one buffer as d_pred and d_target", t);
         }
-        table->term[t] = terms[t];
+        table->term[t] = KernelTerm{terms[t].pred, terms[t].target, terms[t].numerator_mask, terms[t].denominator_mask,
+                                    terms[t].d_pred, terms[t].channels, terms[t].group, terms[t].accumulate, terms[t].weight};
+        if (mirror) {
+            mirror->d_target[t] = terms[t].d_target;
+            if (terms[t].d_target) mirror->wanted |= 1u << t;
+            if (terms[t].d_target && terms[t].accumulate_target) mirror->accumulate |= 1u << t;
+        }
     }
     table->num_terms = num_terms;
     table->num_groups = num_groups;
@@ -332,12 +394,17 @@ extern "C" int snerf_loss_forward(const snerf_loss_term* terms, int num_terms, i
 extern "C" int snerf_loss_backward(const snerf_loss_term* terms, int num_terms, int num_groups, long long num_rays,
                                    const float* scales, const float* upstream, snerf_stream_t stream) {
     TermTable table;
-    if (int st = fill_table(terms, num_terms, num_groups, true, &table)) return st;
+    MirrorTable mirror = {};
+    if (int st = fill_table(terms, num_terms, num_groups, true, &table, &mirror)) return st;
     SNERF_REQUIRE(scales && upstream, "loss_backward: NULL pointer");
     SNERF_REQUIRE(num_rays >= 0, "loss_backward: negative ray count");
     if (num_rays == 0) return SNERF_OK;
-    hipLaunchKernelGGL(loss_backward_kernel, dim3(snerf::stride_grid(num_rays, kBlock)), dim3(kBlock), 0,
-                       (hipStream_t)stream, table, num_rays, scales, upstream);
+    if (mirror.wanted)
+        hipLaunchKernelGGL(loss_backward_mirror_kernel, dim3(snerf::stride_grid(num_rays, kBlock)), dim3(kBlock), 0,
+                           (hipStream_t)stream, table, mirror, num_rays, scales, upstream);
+    else
+        hipLaunchKernelGGL(loss_backward_kernel, dim3(snerf::stride_grid(num_rays, kBlock)), dim3(kBlock), 0,
+                           (hipStream_t)stream, table, num_rays, scales, upstream);
     return snerf::check_launch("loss_backward");
 }
 

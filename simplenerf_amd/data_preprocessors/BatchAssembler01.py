@@ -4,7 +4,10 @@
 ``DataPreprocessor.get_next_batch`` returns in cached-batching train mode (src/data_preprocessors/DataPreprocessor01.py
 :507-551): ``indices``, ``indices_mask_nerf`` [, ``indices_mask_sparse_depth``], ``iter_num``, ``num_frames``, ``rays_o``,
 ``rays_d``, ``view_dirs``, ``pixel_id``, ``target_rgb``, ``near``, ``far`` [, ``rays_o_ndc``, ``rays_d_ndc``,
-``near_ndc``, ``far_ndc``] [, ``sparse_depth_values``, ``sparse_depth_errors``, ``sparse_depth_values_ndc``] and
+``near_ndc``, ``far_ndc``] [, ``sparse_depth_values``, ``sparse_depth_errors``, ``sparse_depth_values_ndc``]
+[, ``dense_depth_values``, ``dense_depth_weights``, ``dense_depth_values_ndc`` -- with ``configs['data_loader']['dense_depth']``,
+the reference's switch (:35): each (n, 1), the pixel-ray rows gathered from the scene's per-pixel tables, every other row -1
+(load_dense_depth_cached_batch, :704-722), by one more launch that reads the same device index buffer as the assembly] and
 ``common_data`` = {poses, intrinsics, images (each with a leading per-GPU axis of ``len(configs['device'])``, default 1),
 resolution}.
 
@@ -12,7 +15,8 @@ resolution}.
 recentring and sparse-depth rasterisation stay outside this build (out of scope):
     poses (V,4,4) processed camera-to-world, intrinsics (V,3,3), images (V,h,w,3) float in [0,1], resolution (h,w),
     near, far [, near_ndc, far_ndc], frame_nums (V,), and optionally the dense (V*h*w,) tables sparse_depths,
-    sparse_errors, sparse_depths_ndc (<= 0 / -1 where a pixel has no sparse depth).
+    sparse_errors, sparse_depths_ndc (<= 0 / -1 where a pixel has no sparse depth), and dense_depths,
+    dense_depth_weights, dense_depths_ndc (what preprocess_dense_depth_data leaves, :465-478; -1 where a pixel has none).
 
 What differs from the reference, by design:
   * no ray cache: rows are recomputed from the cameras in the assembly kernel (bit-identical values);
@@ -72,6 +76,17 @@ class BatchAssembler:
                 raise RuntimeError("configs['data_loader']['sparse_depth'] is set but the scene has no 'sparse_depths' table")
             # candidates = pixels with a sparse depth (numpy.where(sparse_depths > 0), :441); built once at start-up
             self.sparse_candidates = torch.nonzero(self.sparse['sparse_depths'] > 0).reshape(-1).contiguous()
+        self.dense_depth_needed = 'dense_depth' in loader
+        self.dense = {k: (t(scene[k]).reshape(-1) if scene.get(k) is not None else None)
+                      for k in ('dense_depths', 'dense_depth_weights', 'dense_depths_ndc')}
+        if self.dense_depth_needed:
+            missing = [k for k in ('dense_depths', 'dense_depth_weights') + (('dense_depths_ndc',) if self.ndc else ())
+                       if self.dense[k] is None]
+            if missing:
+                raise RuntimeError(f"configs['data_loader']['dense_depth'] is set but the scene has no {', '.join(missing)} table")
+            for k, table in self.dense.items():
+                if table is not None and table.shape[0] != self.num_views * h * w:
+                    raise RuntimeError(f'{k}: {table.shape[0]} entries, expected {self.num_views}*{h}*{w} (one per pixel)')
         fraction, iterations = loader.get('precrop_fraction', 1), loader.get('precrop_iterations', 0)
         self.crop = (0, h, 0, w)
         if fraction < 1 and 0 < iterations:      # generate_indices(iter_num=0), :258-265
@@ -164,6 +179,9 @@ class BatchAssembler:
             out['indices_mask_sparse_depth'] = batch.pop('indices_mask_sparse_depth')
         out.update(iter_num=iter_num, num_frames=self.num_views)
         out.update(batch)
+        if self.dense_depth_needed:
+            out.update(ops.gather_dense_depth(indices, num_pixel, self.dense['dense_depths'], self.dense['dense_depth_weights'],
+                                              self.dense['dense_depths_ndc'] if self.ndc else None))
         # shared tensors with the leading per-GPU axis of the reference (:545-551): one copy per entry of configs['device'], so
         # that DataParallel's scatter hands one to each replica; an expanded view, not a copy (one device: the plain [None] view)
         copies = self.num_replicas

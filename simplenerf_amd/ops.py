@@ -588,11 +588,14 @@ def to_display(rgb: Optional[Tensor], depth: Optional[Tensor] = None, colour: bo
 
 # ---------------------------------------------------------------------------------------------- f1 losses
 class LossTermSpec:
-    """One masked mean-squared-error term of the fused loss evaluation (struct snerf_loss_term)."""
-    __slots__ = ('pred', 'target', 'numerator_mask', 'denominator_mask', 'group', 'weight')
+    """One masked mean-squared-error term of the fused loss evaluation (struct snerf_loss_term).  ``two_sided``: the
+    backward may also be asked for the gradient of ``target`` (the exact negation of ``pred``'s); the value is that of
+    the one-sided term."""
+    __slots__ = ('pred', 'target', 'numerator_mask', 'denominator_mask', 'group', 'weight', 'two_sided')
 
     def __init__(self, pred: Tensor, target: Tensor, numerator_mask: Optional[Tensor], denominator_mask: Optional[Tensor],
-                 group: int, weight: float):
+                 group: int, weight: float, two_sided: bool = False):
+        self.two_sided = bool(two_sided)
         n = pred.shape[0]
         self.pred = _dev(pred, 'loss pred')
         self.target = _dev(target, 'loss target', tuple(pred.shape))
@@ -616,7 +619,8 @@ def _mask(t: Optional[Tensor], name: str, n: int) -> Optional[Tensor]:
 _loss_workspaces: Dict[torch.device, Tensor] = {}
 
 
-def _loss_table(terms: List[LossTermSpec], grads: Optional[List[Optional[Tensor]]]):
+def _loss_table(terms: List[LossTermSpec], grads: Optional[List[Optional[Tensor]]],
+                target_grads: Optional[List[Optional[Tensor]]] = None):
     if not 1 <= len(terms) <= _lib.LOSS_MAX_TERMS:
         raise RuntimeError(f'fused loss: {len(terms)} terms, the kernel table holds 1..{_lib.LOSS_MAX_TERMS}')
     table = (_lib.LossTerm * len(terms))()
@@ -628,11 +632,15 @@ def _loss_table(terms: List[LossTermSpec], grads: Optional[List[Optional[Tensor]
         e.denominator_mask = 0 if t.denominator_mask is None else t.denominator_mask.data_ptr()
         e.channels = 1 if t.pred.dim() == 1 else t.pred.shape[1]
         e.group, e.weight = t.group, t.weight
-        e.d_pred, e.accumulate = 0, 0
+        e.d_pred, e.accumulate, e.d_target, e.accumulate_target = 0, 0, 0, 0
         if grads is not None and grads[i] is not None:
             e.d_pred = grads[i].data_ptr()
             e.accumulate = int(e.d_pred in seen)
             seen.add(e.d_pred)
+        if target_grads is not None and target_grads[i] is not None:
+            e.d_target = target_grads[i].data_ptr()
+            e.accumulate_target = int(e.d_target in seen)
+            seen.add(e.d_target)
     return table
 
 
@@ -656,28 +664,35 @@ def loss_forward(terms: List[LossTermSpec], num_groups: int):
 
 
 def loss_backward(terms: List[LossTermSpec], num_groups: int, scales: Tensor, upstream: Tensor,
-                  wanted: List[bool]) -> List[Optional[Tensor]]:
-    """Gradient of every term's pred (None where ``wanted[i]`` is false).  Terms that share a pred tensor share one
-    buffer holding the sum.  One launch."""
+                  wanted: List[bool], wanted_target: Optional[List[bool]] = None):
+    """Gradient of every term's pred (None where ``wanted[i]`` is false).  Terms that share a tensor share one buffer
+    holding the sum.  One launch.  ``wanted_target`` (two-sided terms only): also the gradient of those terms' targets;
+    the result is then the pair (pred gradients, target gradients), and a tensor that is pred of one term and target of
+    another has ONE buffer, in both lists, holding the sum over both roles."""
     lib = _lib.load()
     n = terms[0].pred.shape[0]
     buffers: Dict[int, Tensor] = {}
-    grads: List[Optional[Tensor]] = []
-    for t, want in zip(terms, wanted):
-        if not want:
-            grads.append(None)
-            continue
-        key = t.pred.data_ptr()
+
+    def buffer_of(t: Tensor) -> Tensor:
+        key = t.data_ptr()
         if key not in buffers:
-            buffers[key] = torch.empty_like(t.pred)
-        grads.append(buffers[key])
+            buffers[key] = torch.empty_like(t)
+        return buffers[key]
+
+    grads: List[Optional[Tensor]] = [buffer_of(t.pred) if want else None for t, want in zip(terms, wanted)]
+    target_grads: Optional[List[Optional[Tensor]]] = None
+    if wanted_target is not None:
+        for t, want in zip(terms, wanted_target):
+            if want and not t.two_sided:
+                raise RuntimeError('fused loss: the gradient of a target was asked of a term that is not two_sided')
+        target_grads = [buffer_of(t.target) if want else None for t, want in zip(terms, wanted_target)]
     upstream = _dev(upstream, 'upstream', (len(terms) + num_groups + 1,))
     if n > 0 and buffers:
         with torch.cuda.device(scales.device):
-            st = lib.snerf_loss_backward(_loss_table(terms, grads), len(terms), int(num_groups), n, _ptr(scales),
-                                         _ptr(upstream), _stream())
+            st = lib.snerf_loss_backward(_loss_table(terms, grads, target_grads), len(terms), int(num_groups), n,
+                                         _ptr(scales), _ptr(upstream), _stream())
         _lib.check(st, 'snerf_loss_backward')
-    return grads
+    return grads if wanted_target is None else (grads, target_grads)
 
 
 def patch_consistency_masks(rays_o: Tensor, rays_d: Tensor, depth1: Tensor, depth2: Tensor, ray_mask: Optional[Tensor],
@@ -804,6 +819,38 @@ def assemble_batch(indices: Tensor, num_pixel_rays: int, table: Tensor, resoluti
                                       int(first_pixel_row + num_pixel_rays if first_sparse_row is None else first_sparse_row),
                                       ctypes.byref(b), _stream())
     _lib.check(st, 'snerf_assemble_batch')
+    return out
+
+
+def gather_dense_depth(indices: Tensor, num_pixel_rays: int, depths: Tensor, weights: Tensor,
+                       depths_ndc: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """One launch: the dense-depth columns of a batch, ``dense_depth_values``, ``dense_depth_weights`` [,
+    ``dense_depth_values_ndc``], each (n, 1) -- the first ``num_pixel_rays`` rows gather the per-pixel tables (flat,
+    num_views*height*width) at ``indices`` (the int64 GPU tensor ``assemble_batch`` reads), every other row holds -1."""
+    lib = _lib.load()
+    if not indices.is_cuda or indices.dtype != torch.int64 or indices.dim() != 1:
+        raise RuntimeError(f'indices: expected a 1-D int64 GPU tensor, got {indices.dtype} {tuple(indices.shape)} on {indices.device}')
+    indices = indices.contiguous()
+    n, dev = indices.shape[0], indices.device
+    depths = _dev(depths, 'dense_depths')
+    if depths.dim() != 1:
+        raise RuntimeError(f'dense_depths: expected a flat per-pixel table, got {tuple(depths.shape)}')
+    pixels = depths.shape[0]
+    weights = _dev(weights, 'dense_depth_weights', (pixels,))
+    depths_ndc = _dev(depths_ndc, 'dense_depths_ndc', (pixels,))
+    if not 0 <= int(num_pixel_rays) <= n:
+        raise RuntimeError(f'gather_dense_depth: {num_pixel_rays} pixel rays of {n} rows')
+    out = {'dense_depth_values': torch.empty((n, 1), dtype=torch.float32, device=dev),
+           'dense_depth_weights': torch.empty((n, 1), dtype=torch.float32, device=dev)}
+    if depths_ndc is not None:
+        out['dense_depth_values_ndc'] = torch.empty((n, 1), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    with torch.cuda.device(dev):
+        st = lib.snerf_gather_dense_depth(ctypes.c_void_p(indices.data_ptr()), n, int(num_pixel_rays), pixels, _ptr(depths),
+                                          _ptr(weights), _ptr(depths_ndc), _ptr(out['dense_depth_values']),
+                                          _ptr(out['dense_depth_weights']), _ptr(out.get('dense_depth_values_ndc')), _stream())
+    _lib.check(st, 'snerf_gather_dense_depth')
     return out
 
 

@@ -260,6 +260,16 @@ def loss_configs(iter_weighted: bool = True) -> list:
     ]
 
 
+def loss_configs01(iter_weighted: bool = True, dense: bool = False) -> list:
+    """The shipped MSE and sparse-depth losses with the plain (01) consistency losses the experiment dictionaries carry
+    commented out (src/NerfLlffTrainerTester01.py:387, :401, :415) in place of the 02 forms [, and DenseDepthMSE01]."""
+    late = {'iter_weights': {'0': 0, '10000': 0.1}} if iter_weighted else {'weight': 0.1}
+    return loss_configs()[:6] + [
+        {'name': 'PointsAugmentationDepthLoss01', **late}, {'name': 'ViewsAugmentationDepthLoss01', **late},
+        {'name': 'CoarseFineConsistencyLoss01', **late},
+    ] + ([{'name': 'DenseDepthMSE01', 'weight': 0.1}] if dense else [])
+
+
 def loss_batch(scene: dict, num_rays: int, num_sparse: int, seed: int = 0) -> Dict[str, numpy.ndarray]:
     """Seeded stand-ins for one training batch and the model outputs the losses read: ``num_rays`` pixel rays followed
     by ``num_sparse`` sparse-depth rays (the layout of load_cached_next_batch, DataPreprocessor01.py:514-584), depth
@@ -304,6 +314,52 @@ def loss_batch(scene: dict, num_rays: int, num_sparse: int, seed: int = 0) -> Di
     }
 
 
+# the cases of tests/golden/losses01_*.npz (tools/make_golden_losses01.py runs the reference's classes on them)
+#   losses: '01' = loss_configs01(), '01+dense' = with DenseDepthMSE01, 'all' = the nine shipped losses + those four (16 terms)
+LOSS01_CASES = {
+    'world': dict(scene_seed=0, batch_seed=0, num_rays=320, num_sparse=64, iter_num=20000, ndc=False, losses='01'),
+    'ndc': dict(scene_seed=1, batch_seed=2, num_rays=288, num_sparse=96, iter_num=20000, ndc=True, losses='01'),
+    'early': dict(scene_seed=0, batch_seed=0, num_rays=320, num_sparse=64, iter_num=0, ndc=False, losses='01'),
+    'dense': dict(scene_seed=0, batch_seed=4, num_rays=320, num_sparse=64, iter_num=20000, ndc=False, losses='01+dense',
+                  coarse_only=True),
+    'dense_fine': dict(scene_seed=1, batch_seed=6, num_rays=320, num_sparse=64, iter_num=20000, ndc=True, losses='all'),
+    'empty': dict(scene_seed=0, batch_seed=5, num_rays=0, num_sparse=8, iter_num=20000, ndc=False, losses='01+dense'),
+}
+LOSS01_OUTPUT_KEYS = ('rgb_coarse', 'rgb_fine', 'points_augmentation_rgb_coarse', 'views_augmentation_rgb_coarse',
+                      'depth_coarse', 'depth_fine', 'points_augmentation_depth_coarse', 'views_augmentation_depth_coarse')
+
+
+def loss01_case(name: str):
+    """-> (configs, scene, batch, output keys) of one ``LOSS01_CASES`` entry: the config-3 model (``coarse_only``: without
+    its fine MLP), a ``loss_batch`` with the ``dense_depth_values`` column of ``dense_depth_tables`` where the list has
+    DenseDepthMSE01."""
+    case = LOSS01_CASES[name]
+    scene = synth_scene(case['scene_seed'])
+    batch = loss_batch(scene, case['num_rays'], case['num_sparse'], case['batch_seed'])
+    # loss_batch plants a few wild depth estimates (1e6, -40, ...) for the patch decisions; an un-masked squared error would
+    # consist of nothing else, so the plain losses see them clipped to the scene's depth range
+    for key in batch:
+        if 'depth_' in key and batch[key].ndim == 1:
+            batch[key] = numpy.clip(batch[key], 0.5, 12.0)
+    configs = make_configs('config3')
+    configs['data_loader']['ndc'] = case['ndc']
+    configs['data_loader']['sparse_depth'] = {}
+    keys = LOSS01_OUTPUT_KEYS
+    if case.get('coarse_only'):
+        del configs['model']['fine_mlp']
+        keys = tuple(k for k in keys if not k.endswith('_fine'))
+    dense = case['losses'] != '01'
+    if case['losses'] == 'all':
+        configs['losses'] = loss_configs() + loss_configs01(dense=True)[6:]
+    else:
+        configs['losses'] = loss_configs01(dense=dense)
+    if dense:
+        configs['data_loader']['dense_depth'] = {}
+        tables = dense_depth_tables(scene, case['scene_seed'])
+        batch['dense_depth_values'] = dense_depth_column(batch, tables, scene)
+    return configs, scene, batch, keys
+
+
 def optim_case(seed: int = 0) -> dict:
     """Seeded parameters and per-step gradients for the optimiser fixtures: a few tensor shapes (odd sizes included)
     with gradients spanning many magnitudes (zeros and denormal-sized second moments included), stepped at the
@@ -324,12 +380,40 @@ def optim_case(seed: int = 0) -> dict:
     return {'params': params, 'grads': grads, 'iters': iters, 'record': (1, 2, 6)}
 
 
+def dense_depth_tables(scene: dict, seed: int = 0, missing_fraction: float = 0.02) -> Dict[str, numpy.ndarray]:
+    """Per-pixel dense-depth tables for a ``synth_scene`` in the form ``BatchAssembler`` takes (what the reference's
+    preprocess_dense_depth_data leaves, DataPreprocessor01.py:465-478): ``dense_depths`` = true plane depth + noise,
+    ``dense_depth_weights`` in (0, 1], ``dense_depths_ndc``; a random ``missing_fraction`` of the pixels holds -1 in the
+    depth tables ("no depth").  Flat float32 arrays of num_views*height*width entries."""
+    rng = numpy.random.RandomState(seed + 70)
+    true = scene['true_depth']
+    missing = rng.uniform(size=true.shape) < missing_fraction
+    # (depths on a 1/128 grid, weights on a 1/256 grid: a fixture that stores the tables compresses)
+    depth = numpy.where(missing, -1.0, numpy.round(128 * (true + 0.05 * rng.standard_normal(true.shape))) / 128).astype(numpy.float32)
+    weights = (rng.randint(13, 257, size=true.shape) / 256).astype(numpy.float32)
+    ndc = numpy.where(missing, -1.0, 1.0 - 1.0 / numpy.maximum(depth, 1e-3)).astype(numpy.float32)
+    return {'dense_depths': depth.reshape(-1), 'dense_depth_weights': weights.reshape(-1), 'dense_depths_ndc': ndc.reshape(-1)}
+
+
+def dense_depth_column(batch: Dict[str, numpy.ndarray], tables: Dict[str, numpy.ndarray], scene: dict,
+                       key: str = 'dense_depths') -> numpy.ndarray:
+    """The (n, 1) batch column the loader makes of a dense table for a ``loss_batch``: the pixel-ray rows gather the table at
+    their pixel, every other row holds -1 (load_dense_depth_cached_batch, DataPreprocessor01.py:704-722)."""
+    h, w = scene['resolution']
+    pid = batch['pixel_id'].astype(numpy.int64)
+    column = numpy.full((pid.shape[0], 1), -1.0, dtype=numpy.float32)
+    mask = batch['indices_mask_nerf']
+    column[mask, 0] = tables[key][(pid[:, 0] * h + pid[:, 2]) * w + pid[:, 1]][mask]
+    return column
+
+
 def training_scene(seed: int = 0, num_views: int = 3, height: int = 756, width: int = 1008, sparse_fraction: float = 2e-3,
-                   sparse_points: int = None) -> dict:
+                   sparse_points: int = None, dense_depth: bool = False) -> dict:
     """``synth_scene`` at a training resolution in the form ``BatchAssembler`` takes, plus dense sparse-depth tables
     (true plane depth + noise on a random ``sparse_fraction`` of the pixels, -1 elsewhere).
     ``sparse_points``: exactly that many pixels carry a sparse depth instead (a benchmark wants an epoch that is a whole
-    number of batches: with the default ~4 570 points every third 2048-row batch of the epoch is 476 rows short)."""
+    number of batches: with the default ~4 570 points every third 2048-row batch of the epoch is 476 rows short).
+    ``dense_depth``: the scene also carries ``dense_depth_tables``."""
     scene = synth_scene(seed, num_views, height, width)
     rng = numpy.random.RandomState(seed + 50)
     has = rng.uniform(size=scene['true_depth'].shape) < sparse_fraction
@@ -339,7 +423,8 @@ def training_scene(seed: int = 0, num_views: int = 3, height: int = 756, width: 
         has = has.reshape(scene['true_depth'].shape)
     depth = numpy.where(has, scene['true_depth'] + 0.05 * rng.standard_normal(has.shape), -1.0).astype(numpy.float32)
     error = numpy.where(has, rng.uniform(0.1, 2.0, size=has.shape), -1.0).astype(numpy.float32)
-    return {**scene, 'near': 1.0, 'far': 6.0, 'near_ndc': 0.0, 'far_ndc': 1.0, 'frame_nums': list(range(num_views)),
+    dense = dense_depth_tables(scene, seed) if dense_depth else {}
+    return {**scene, **dense, 'near': 1.0, 'far': 6.0, 'near_ndc': 0.0, 'far_ndc': 1.0, 'frame_nums': list(range(num_views)),
             'sparse_depths': depth.reshape(-1), 'sparse_errors': error.reshape(-1),
             'sparse_depths_ndc': numpy.where(has, 1.0 - 1.0 / numpy.maximum(depth, 1e-3), -1.0).astype(numpy.float32).reshape(-1)}
 
