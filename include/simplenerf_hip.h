@@ -379,6 +379,50 @@ int snerf_to_display(const float* rgb, const float* depth, long long num_rays, u
                      snerf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Q1  scoring a rendered frame on the device: the sums behind the reference's frame metrics (src/qa/01_RMSE, 02_PSNR,
+ * 03_SSIM, 05_DepthRMSE, 06_DepthMAE, 07_DepthSROCC and their masked forms 11-13, 15-17); the host turns them into the
+ * metrics (simplenerf_amd/qa.py).  These functions were ADDED within ABI version 10: no existing struct or signature
+ * changed, so SNERF_ABI_VERSION stays 10 (a caller that needs them checks that the symbol exists).
+ *   gt, eval   device (height, width, 3) uint8 -- the image layout of the display conversion above -- or device (count) fp32 depths
+ *   mask       device (height, width) / (count) bytes, non-zero = counted; NULL = no mask
+ *   workspace  device scratch, at least the workspace-bytes query below for the frame (for the 1-D calls: any height * width >=
+ *              count); no initial state is needed, and calls enqueued on ONE stream may share it
+ * Image sums are exact 64-bit integers, everything else is fp64; every reduction folds per-workgroup partial sums in a
+ * fixed order (no atomics), so two calls on the same input return the same bits.  Like every entry point these only
+ * enqueue on `stream`: no allocation, no synchronisation; a non-zero return leaves its message for the last-error query.
+ */
+long long snerf_metrics_workspace_bytes(int height, int width);
+
+/* sums  device (3) int64: sum (gt - eval)^2 over all height*width*3 values; the same over the masked pixels; number of masked
+ *       pixels (both 0 without a mask).  MSE = sums[0] / (3 height width), masked MSE = sums[1] / (3 sums[2]). */
+int snerf_image_error_sums(const unsigned char* gt, const unsigned char* eval, const unsigned char* mask, int height,
+                           int width, long long* sums, void* workspace, snerf_stream_t stream);
+
+/* Gaussian-weighted SSIM map S per channel as skimage's structural_similarity computes it with gaussian_weights=True,
+ * sigma=1.5, use_sample_covariance=False, data_range=255: an 11-tap separable window (truncate 3.5) with scipy's `reflect`
+ * boundary, v = E[x^2] - E[x]^2, S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)).  With a mask, eval is
+ * replaced by gt on the unmasked pixels first (13_MaskedSSIM).  height, width >= 11.
+ *   sums   device (2) fp64: sum of S over the map cropped by 5 pixels on every side (SSIM = sums[0] / (3 (height-10)(width-10)));
+ *          sum of S over the masked pixels of the whole map (MaskedSSIM = sums[1] / (3 #masked)) -- over every pixel without a mask
+ *   s_map  device (height, width, 3) fp64 or NULL: the whole map S, border included */
+int snerf_ssim_sums(const unsigned char* gt, const unsigned char* eval, const unsigned char* mask, int height, int width,
+                    double* sums, double* s_map, void* workspace, snerf_stream_t stream);
+
+/* e = gt * gt_scale - eval * eval_scale in fp64 (the per-side factors of the reference's get_depth_scale, applied first).
+ *   sorted_gt  device (count): gt sorted ascending, or NULL when the median is not wanted
+ *   sums       device (4) fp64: sum |e|, sum e^2, number of pixels counted (masked, or all); numpy.median(gt * gt_scale) over ALL of
+ *              gt, mask or not (mean of the two middle values for an even count; untouched when sorted_gt is NULL) */
+int snerf_depth_error_sums(const float* gt, const float* eval, double gt_scale, double eval_scale, const unsigned char* mask,
+                           long long count, const float* sorted_gt, double* sums, void* workspace, snerf_stream_t stream);
+
+/* Spearman's rank correlation of (x, y) from tie-averaged ranks: the rank of each value is found in the sorted copy by a lower
+ * and an upper bound search (no walk along a run of ties) and centred by the exact mean rank (count + 1) / 2.
+ *   sorted_x, sorted_y  device (count): x and y sorted ascending
+ *   sums  device (3) fp64: sum rx ry, sum rx^2, sum ry^2;  SROCC = sums[0] / sqrt(sums[1] sums[2]) */
+int snerf_rank_correlation_sums(const float* x, const float* y, const float* sorted_x, const float* sorted_y, long long count,
+                                double* sums, void* workspace, snerf_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Opt-in event timing of the dominant kernels (the measurement row, SURVEY 8d: "achieved" of the roofline is measured
  * live with HIP events on the stream the kernel is launched on).  While enabled, every snerf_mlp_forward[_train] launch
  * (kind SNERF_PROFILE_MLP_FORWARD) and every snerf_mlp_backward call (SNERF_PROFILE_MLP_BACKWARD) -- also those issued

@@ -126,6 +126,12 @@ SIGNATURES = {
                                 _FP, _FP, _FP, _FP, c_void_p]),
     'snerf_to_display': (c_int, [_FP, _FP, c_longlong, _FP, _FP, c_void_p]),
     'snerf_resample_depths': (c_int, [_FP, _FP, c_longlong, c_int, c_int, _FP, _FP, c_void_p]),
+    # frame metrics (Q1)
+    'snerf_metrics_workspace_bytes': (c_longlong, [c_int, c_int]),
+    'snerf_image_error_sums': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'snerf_ssim_sums': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'snerf_depth_error_sums': (c_int, [_FP, _FP, c_double, c_double, c_void_p, c_longlong, _FP, c_void_p, c_void_p, c_void_p]),
+    'snerf_rank_correlation_sums': (c_int, [_FP, _FP, _FP, _FP, c_longlong, c_void_p, c_void_p, c_void_p]),
     # include/simplenerf_train.h
     'snerf_loss_workspace_bytes': (c_longlong, []),
     'snerf_loss_forward': (c_int, [POINTER(LossTerm), c_int, c_int, c_longlong, _FP, _FP, c_void_p, c_void_p]),

@@ -167,6 +167,48 @@ def predict_frame(model, configs: dict, camera: dict, device, rank: int = 0, wor
     return retrieve_inference_outputs(configs, camera['resolution'], frame)
 
 
+@torch.no_grad()
+def evaluate_frames(model, configs: dict, frames, device, rank: int = 0, world_size: int = 1, ray_block: int = 65536,
+                    collective: Optional[bool] = None) -> Optional[dict]:
+    """The reference's QA stage over a test set (src/qa/*), without the frames leaving the device: every frame is rendered
+    through the path of ``predict_frame``, converted for display there (uint8 colour, depth clipped at 0) and scored against its
+    targets by ``qa.image_metrics`` / ``qa.depth_metrics`` -- only the metrics' scalar sums cross to the host.
+
+    ``frames``: iterable of {'frame_num', 'camera', 'image' (h,w,3) uint8 [, 'depth' (h,w) float32, 'mask' (h,w) bool,
+    'depth_scale', 'gt_depth_scale' (the reference's per-side depth factors; default 1)]}, arrays or tensors.
+    Returns {'frames': [{'frame_num': ., metric: value rounded to 4 decimals, ...}], 'average': {metric: value}} with the
+    reference's bookkeeping (``qa.summarise``) plus 'unrounded', the per-frame values before rounding.  With world_size > 1 each
+    rank renders its block of every frame, rank 0 scores and the other ranks return None."""
+    from . import qa
+    ndc = bool(configs['data_loader']['ndc'])
+    suffix = '_fine' if 'fine_mlp' in configs['model'] else '_coarse'
+    keys = [f'rgb{suffix}', f'depth{suffix}']
+
+    def on_device(value):
+        return torch.as_tensor(value).to(device)      # (dtypes are checked by the metric functions, not converted)
+
+    rows = []
+    for frame in frames:
+        camera = frame['camera']
+        h, w = int(camera['resolution'][0]), int(camera['resolution'][1])
+        rendered = render_frame(model, camera, ndc, device, keys, rank, world_size, ray_block, collective)
+        if rendered is None:
+            continue
+        image, depth = ops.to_display(rendered[f'rgb{suffix}'].reshape(h * w, 3), rendered[f'depth{suffix}'].reshape(h * w))
+        mask = on_device(frame['mask']) if frame.get('mask') is not None else None
+        row = {'frame_num': frame['frame_num']}
+        row.update(qa.image_metrics(image.reshape(h, w, 3), on_device(frame['image']), mask))
+        if frame.get('depth') is not None:
+            row.update(qa.depth_metrics(depth.reshape(h, w), on_device(frame['depth']),
+                                        float(frame.get('depth_scale', 1.0)), float(frame.get('gt_depth_scale', 1.0)), mask))
+        rows.append(row)
+    if rank != 0 and (world_size > 1 if collective is None else collective):
+        return None
+    table = qa.summarise(rows)
+    table['unrounded'] = rows
+    return table
+
+
 def allreduce_gradients(parameters, world_size: int, group=None, force: bool = False) -> None:
     """Training with rays sharded over ranks: average every parameter gradient across ranks with ONE collective
     (all gradients flattened into a single buffer: 2 265 488 floats = 9.06 MB for the 4-MLP model).

@@ -586,6 +586,117 @@ def to_display(rgb: Optional[Tensor], depth: Optional[Tensor] = None, colour: bo
     return image, depth_out
 
 
+# ---------------------------------------------------------------------------------------------- Q1 frame metrics
+def _typed(t, name: str, dtypes, shape=None) -> Tensor:
+    """Validate a device operand of one of ``dtypes`` (the metric inputs are uint8 / bool / float32); contiguous on return."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f'{name}: expected a tensor on the GPU (the HIP renderer has no CPU path), got '
+                           f'{type(t).__name__}{"" if not isinstance(t, torch.Tensor) else " on " + str(t.device)}')
+    if t.dtype not in dtypes:
+        raise RuntimeError(f'{name}: expected {" or ".join(str(d).replace("torch.", "") for d in dtypes)}, got {t.dtype}')
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f'{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}')
+    return t.detach().contiguous()
+
+
+SSIM_WINDOW = 11     # taps of the Gaussian window (sigma 1.5, truncate 3.5): the shortest side an image may have
+
+# scratch of the metric reductions (per-workgroup partial sums), one per device, grown on demand; calls on one device are
+# ordered by the stream they are enqueued on
+_metric_workspaces: Dict[torch.device, Tensor] = {}
+
+
+def _metric_workspace(lib, dev: torch.device, height: int, width: int) -> Tensor:
+    need = int(lib.snerf_metrics_workspace_bytes(int(height), int(width)))
+    ws = _metric_workspaces.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = _metric_workspaces[dev] = torch.empty((need,), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _image_pair(gt: Tensor, image: Tensor, mask: Optional[Tensor]):
+    gt = _typed(gt, 'gt_image', (torch.uint8,))
+    if gt.dim() != 3 or gt.shape[2] != 3:
+        raise RuntimeError(f'gt_image: expected shape (h, w, 3), got {tuple(gt.shape)}')
+    h, w = int(gt.shape[0]), int(gt.shape[1])
+    image = _typed(image, 'eval_image', (torch.uint8,), (h, w, 3))
+    if mask is not None:
+        mask = _typed(mask, 'mask', (torch.bool, torch.uint8), (h, w))
+    return gt, image, mask, h, w
+
+
+def image_error_sums(gt: Tensor, image: Tensor, mask: Optional[Tensor] = None) -> Tensor:
+    """-> int64 (3) on the device: sum (gt - eval)^2 over h*w*3, the same over the masked pixels, the masked pixel count."""
+    gt, image, mask, h, w = _image_pair(gt, image, mask)
+    if h < 1 or w < 1:
+        raise RuntimeError(f'gt_image: empty image {tuple(gt.shape)}')
+    sums = torch.empty((3,), dtype=torch.int64, device=gt.device)
+    lib = _lib.load()
+    with torch.cuda.device(gt.device):
+        ws = _metric_workspace(lib, gt.device, h, w)
+        st = lib.snerf_image_error_sums(_ptr(gt), _ptr(image), _ptr(mask), h, w, _ptr(sums), _ptr(ws), _stream())
+    _lib.check(st, 'snerf_image_error_sums')
+    return sums
+
+
+def ssim_sums(gt: Tensor, image: Tensor, mask: Optional[Tensor] = None, return_map: bool = False):
+    """-> float64 (2) on the device: sum of the SSIM map S cropped by 5 pixels per side; sum of S over the masked pixels (every
+    pixel without a mask) -- with a mask, S is that of (gt, where(mask, eval, gt)).  ``return_map``: also S, float64 (h,w,3)."""
+    gt, image, mask, h, w = _image_pair(gt, image, mask)
+    if min(h, w) < SSIM_WINDOW:
+        raise RuntimeError(f'gt_image: the {SSIM_WINDOW}-tap SSIM window exceeds the image extent {h} x {w}: every side must be '
+                           f'at least {SSIM_WINDOW}')
+    sums = torch.empty((2,), dtype=torch.float64, device=gt.device)
+    s_map = torch.empty((h, w, 3), dtype=torch.float64, device=gt.device) if return_map else None
+    lib = _lib.load()
+    with torch.cuda.device(gt.device):
+        ws = _metric_workspace(lib, gt.device, h, w)
+        st = lib.snerf_ssim_sums(_ptr(gt), _ptr(image), _ptr(mask), h, w, _ptr(sums), _ptr(s_map), _ptr(ws), _stream())
+    _lib.check(st, 'snerf_ssim_sums')
+    return (sums, s_map) if return_map else sums
+
+
+def depth_error_sums(gt: Tensor, depth: Tensor, gt_scale: float = 1.0, eval_scale: float = 1.0, mask: Optional[Tensor] = None,
+                     sorted_gt: Optional[Tensor] = None) -> Tensor:
+    """-> float64 (4) on the device: sum |e|, sum e^2, pixels counted, median(gt * gt_scale) (NaN without ``sorted_gt``) for
+    e = gt * gt_scale - eval * eval_scale on the masked (or all) pixels."""
+    gt = _typed(gt, 'gt_depth', (torch.float32,))
+    depth = _typed(depth, 'eval_depth', (torch.float32,), tuple(gt.shape))
+    n = gt.numel()
+    if n < 1:
+        raise RuntimeError(f'gt_depth: empty depth map {tuple(gt.shape)}')
+    if mask is not None:
+        mask = _typed(mask, 'mask', (torch.bool, torch.uint8), tuple(gt.shape))
+    if sorted_gt is not None:
+        sorted_gt = _typed(sorted_gt, 'sorted_gt', (torch.float32,), (n,))
+    sums = torch.full((4,), float('nan'), dtype=torch.float64, device=gt.device)
+    lib = _lib.load()
+    with torch.cuda.device(gt.device):
+        ws = _metric_workspace(lib, gt.device, 1, 1)
+        st = lib.snerf_depth_error_sums(_ptr(gt), _ptr(depth), float(gt_scale), float(eval_scale), _ptr(mask), n, _ptr(sorted_gt),
+                                        _ptr(sums), _ptr(ws), _stream())
+    _lib.check(st, 'snerf_depth_error_sums')
+    return sums
+
+
+def rank_correlation_sums(x: Tensor, y: Tensor, sorted_x: Tensor, sorted_y: Tensor) -> Tensor:
+    """-> float64 (3) on the device: sum rx ry, sum rx^2, sum ry^2 of the centred tie-averaged ranks of the flat x, y."""
+    x = _typed(x, 'x', (torch.float32,))
+    n = x.numel()
+    if x.dim() != 1 or n < 1:
+        raise RuntimeError(f'x: expected a non-empty flat tensor, got {tuple(x.shape)}')
+    y = _typed(y, 'y', (torch.float32,), (n,))
+    sorted_x = _typed(sorted_x, 'sorted_x', (torch.float32,), (n,))
+    sorted_y = _typed(sorted_y, 'sorted_y', (torch.float32,), (n,))
+    sums = torch.empty((3,), dtype=torch.float64, device=x.device)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        ws = _metric_workspace(lib, x.device, 1, 1)
+        st = lib.snerf_rank_correlation_sums(_ptr(x), _ptr(y), _ptr(sorted_x), _ptr(sorted_y), n, _ptr(sums), _ptr(ws), _stream())
+    _lib.check(st, 'snerf_rank_correlation_sums')
+    return sums
+
+
 # ---------------------------------------------------------------------------------------------- f1 losses
 class LossTermSpec:
     """One masked mean-squared-error term of the fused loss evaluation (struct snerf_loss_term).  ``two_sided``: the

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """End-to-end training sanity run on one MI355X: the synthetic 3-view plane scene (synth.training_scene at 96x128),
 every stage on the device (BatchAssembler -> SimpleNeRFHip -> LossComputer -> optim.Adam with the NeRF decay), a few
-hundred iterations.  Prints the loss curve and the PSNR of a training view rendered before and after.
+hundred iterations.  Prints the loss curve, the PSNR of a training view
+rendered before and after, and the 8-bit frame metrics of every view.
     python tools/train_demo.py [iterations]            (SNERF_PREC=f16x3 for the split-precision kernels, f16 for the 16-bit mode;
                                                         SNERF_GRAPH=1 replays the pass from one HIP graph; SNERF_SEED=n: initial
                                                         weights, epoch order and training draws of seed n)
@@ -12,6 +13,7 @@ import os
 import sys
 import time
 
+import numpy
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,9 +26,28 @@ from simplenerf_amd.models.ModelFactory import get_model  # noqa: E402
 DEV = torch.device('cuda', 0)
 
 
+def camera_of(scene, view):
+    return {'resolution': scene['resolution'], 'intrinsic': scene['intrinsics'][view], 'pose': scene['poses'][view],
+            'near': scene['near'], 'far': scene['far'], 'near_ndc': 0.0, 'far_ndc': 1.0}
+
+
+def scene_frames(scene):
+    """The scene's views as ``harness.evaluate_frames`` takes them: the 8-bit image the reference's post_process_image would
+    write (clip, round(255 x), uint8) and the true depth."""
+    return [{'frame_num': scene['frame_nums'][v], 'camera': camera_of(scene, v), 'depth': scene['true_depth'][v],
+             'image': numpy.round(numpy.clip(scene['images'][v], 0, 1) * 255).astype('uint8')} for v in range(len(scene['poses']))]
+
+
+def frame_scores(model, cfg, scene):
+    """The reference's frame metrics (8-bit PSNR, SSIM, depth MAE / SROCC ...) of every view, scored on the device."""
+    model.eval()
+    table = harness.evaluate_frames(model, cfg, scene_frames(scene), DEV)
+    model.train()
+    return table
+
+
 def psnr_of_view(model, scene, view):
-    cam = {'resolution': scene['resolution'], 'intrinsic': scene['intrinsics'][view], 'pose': scene['poses'][view],
-           'near': scene['near'], 'far': scene['far'], 'near_ndc': 0.0, 'far_ndc': 1.0}
+    cam = camera_of(scene, view)
     model.eval()
     rgb = harness.render_frame(model, cam, True, DEV, keys=('rgb_fine',))['rgb_fine']
     model.train()
@@ -35,9 +56,9 @@ def psnr_of_view(model, scene, view):
     return -10 * math.log10(max(mse, 1e-12))
 
 
-def run(iters=300, precision='fp32', graph=False, seed=0):
+def run(iters=300, precision='fp32', graph=False, seed=0, with_scores=False):
     """-> the record ``main`` prints.  ``seed`` selects the initial weights (torch.manual_seed), the epoch order and the training
-    draws (configs['seed']); the scene is the same for every seed."""
+    draws (configs['seed']); the scene is the same for every seed.  ``with_scores``: -> (record, the whole ``harness.evaluate_frames`` table)."""
     cfg = synth.training_configs(precision, num_rays=1024, num_sparse=256, seed=seed)
     cfg['sub_batch_size'] = 1280
     cfg['losses'] = synth.loss_configs(iter_weighted=False)      # consistency losses on from the first iteration
@@ -75,8 +96,14 @@ def run(iters=300, precision='fp32', graph=False, seed=0):
     dt = time.perf_counter() - t0
     after = psnr_of_view(model, scene, 0)
     views = [psnr_of_view(model, scene, v) for v in range(len(scene['poses']))]
-    return {'precision': precision, 'graph': graphed is not None, 'seed': seed, 'iterations': iters, 'seconds': dt,
-            'psnr_view0_before': before, 'psnr_view0_after': after, 'psnr_all_views_after': views, 'curve': curve}
+    scores = frame_scores(model, cfg, scene)
+    record = {'precision': precision, 'graph': graphed is not None, 'seed': seed, 'iterations': iters, 'seconds': dt,
+            'psnr_view0_before': before, 'psnr_view0_after': after, 'psnr_all_views_after': views,
+            # the reference's definitions, on the 8-bit frames (qa.image_metrics; the psnr_* keys above are on float colours)
+            'qa_psnr_all_views_after': [row['PSNR'] for row in scores['frames']],
+            'qa_ssim_all_views_after': [row['SSIM'] for row in scores['frames']], 'qa_average_after': scores['average'],
+            'curve': curve}
+    return (record, scores) if with_scores else record
 
 
 def main():
