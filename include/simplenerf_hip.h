@@ -423,6 +423,59 @@ int snerf_rank_correlation_sums(const float* x, const float* y, const float* sor
                                 double* sums, void* workspace, snerf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Q2  the visibility mask of the masked metrics: the reference's src/qa/00_Common/src/mask_generators (Warper.forward_warp,
+ * MaskComputer.compute_mask, "visible in at least two training views").  `views` training depths are splatted into ONE test view of
+ * the same resolution and tested against its depth.  Like Q1 these were ADDED within ABI version 10 (no existing struct or
+ * signature changed; a caller checks that the symbol exists).  The call sequence is project -> a STABLE ascending sort of `keys`
+ * by the caller (sorted keys + the permutation, e.g. torch.sort(keys, stable=True)) -> list_starts -> gather -> combine, all on one
+ * stream.  All arithmetic is fp64 (fp32 depths are widened on load); there is no floating-point atomic: every destination pixel
+ * sums its sources in ascending source order, so two calls on the same input return the same bits.  The calls only enqueue on
+ * `stream`: no allocation, no synchronisation.  views * ((height + 1)(width + 1) + 1) must stay below 2^31, views <= 65535.
+ *
+ * Conventions.  Extrinsics are 4x4 world-to-camera [R t; 0 1], intrinsics 3x3 [f 0 cx; 0 f cy; 0 0 1], x right, y down, z forward,
+ * as in the database's CameraExtrinsics.csv / CameraIntrinsics.csv; depths are z-depths in the extrinsics' units.  The HOST inverts
+ * and composes them in fp64:
+ *   cameras  device (views, 30) fp64, row-major per view: inv(K_train) 3x3 | rows 0..2 of E_test inv(E_train) 3x4 | K_test 3x3
+ * Source pixel (x, y) of a view: p = inv(K_train) (x, y, 1)^T d_train[y, x], q = K_test (T (p, 1))[:3]; padded position
+ * (X, Y) = (q0 / q2 + 1, q1 / q2 + 1), transformed depth Z = q2.  It adds prox / exp(50 L / max L), L = log(1 + clip(Z, 0, 1000)),
+ * max over the view's sources, to the cells (floor | ceil X, floor | ceil Y) clipped to the padded (height + 2, width + 2) grid
+ * (floor and ceil before the clip; an integer coordinate adds twice to one cell), prox = the bilinear proximity of the clipped
+ * position; the padded border is cropped.  Kept as the reference has it: a point behind the test camera (Z < 0) still splats,
+ * with the LARGEST depth weight (its L is 0).  Not pinned by the reference (undefined there): a source whose X, Y or Z is not
+ * finite or whose floor leaves int32, and a view whose max L is 0 -- such a source, or every source of such a view, adds nothing.
+ */
+long long snerf_visibility_mask_workspace_bytes(int views, int height, int width);
+
+/* depth_train  device (views, height, width) fp32
+ * points       device (views, 3, height, width) fp64, written: the planes X, Y, Z of every source
+ * keys         device (views, height, width) int32, written: view * ((height+1)(width+1) + 1) + the source's list -- its unclipped
+ *              floor cell fy * (width + 1) + fx when that lies in [0, height] x [0, width] (only those can reach a cell that survives
+ *              the crop), else (and for an unpinned source) the view's last key, the discard list that is never walked
+ * stats        device (views, 2) fp64, written: max L, max d_train (of the untransformed depth) per view
+ * workspace    device scratch of at least the query above; no initial state */
+int snerf_visibility_mask_project(const float* depth_train, const double* cameras, int views, int height, int width, double* points,
+                                  int* keys, double* stats, void* workspace, snerf_stream_t stream);
+
+/* sorted_keys  device (views * height * width) int32: `keys` sorted ascending
+ * starts       device (views * ((height+1)(width+1) + 1) + 1) int32, written: starts[k] = first sorted position whose key is >= k */
+int snerf_visibility_mask_list_starts(const int* sorted_keys, int views, int height, int width, int* starts, snerf_stream_t stream);
+
+/* order         device (views * height * width) int64: the permutation of the STABLE sort (sorted position -> index into `keys`)
+ * depth_test    device (height, width) fp32
+ * mask_views    device (views, height, width) bytes, written: 1 where weight_sum > 0 and
+ *               |warped_depth - depth_test| < depth_error_threshold * max d_train of that view
+ * warped_depth  device (views, height, width) fp64 or NULL: sum Z weight / sum weight where weight_sum > 0, else 0
+ * weight_sum    device (views, height, width) fp64 or NULL: sum of the weights that landed on the pixel */
+int snerf_visibility_mask_gather(const double* points, const long long* order, const int* starts, const double* stats,
+                                 const float* depth_test, double depth_error_threshold, int views, int height, int width,
+                                 unsigned char* mask_views, double* warped_depth, double* weight_sum, snerf_stream_t stream);
+
+/* mask  device (height, width) bytes, written: 1 where at least min_views (1 .. views) of mask_views are set; the reference's
+ *       numpy.sum(masks, axis=0) > 1 is min_views = 2 */
+int snerf_visibility_mask_combine(const unsigned char* mask_views, int views, int height, int width, int min_views,
+                                  unsigned char* mask, snerf_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Opt-in event timing of the dominant kernels (the measurement row, SURVEY 8d: "achieved" of the roofline is measured
  * live with HIP events on the stream the kernel is launched on).  While enabled, every snerf_mlp_forward[_train] launch
  * (kind SNERF_PROFILE_MLP_FORWARD) and every snerf_mlp_backward call (SNERF_PROFILE_MLP_BACKWARD) -- also those issued

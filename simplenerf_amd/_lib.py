@@ -132,6 +132,13 @@ SIGNATURES = {
     'snerf_ssim_sums': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'snerf_depth_error_sums': (c_int, [_FP, _FP, c_double, c_double, c_void_p, c_longlong, _FP, c_void_p, c_void_p, c_void_p]),
     'snerf_rank_correlation_sums': (c_int, [_FP, _FP, _FP, _FP, c_longlong, c_void_p, c_void_p, c_void_p]),
+    # visibility masks (Q2)
+    'snerf_visibility_mask_workspace_bytes': (c_longlong, [c_int, c_int, c_int]),
+    'snerf_visibility_mask_project': (c_int, [_FP, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'snerf_visibility_mask_list_starts': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'snerf_visibility_mask_gather': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, _FP, c_double, c_int, c_int, c_int, c_void_p,
+                                             c_void_p, c_void_p, c_void_p]),
+    'snerf_visibility_mask_combine': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     # include/simplenerf_train.h
     'snerf_loss_workspace_bytes': (c_longlong, []),
     'snerf_loss_forward': (c_int, [POINTER(LossTerm), c_int, c_int, c_longlong, _FP, _FP, c_void_p, c_void_p]),

@@ -175,7 +175,10 @@ def evaluate_frames(model, configs: dict, frames, device, rank: int = 0, world_s
     targets by ``qa.image_metrics`` / ``qa.depth_metrics`` -- only the metrics' scalar sums cross to the host.
 
     ``frames``: iterable of {'frame_num', 'camera', 'image' (h,w,3) uint8 [, 'depth' (h,w) float32, 'mask' (h,w) bool,
-    'depth_scale', 'gt_depth_scale' (the reference's per-side depth factors; default 1)]}, arrays or tensors.
+    'depth_scale', 'gt_depth_scale' (the reference's per-side depth factors; default 1)]}, arrays or tensors.  Instead of 'mask' a
+    frame may carry 'mask_views': {'depth_train' (T,h,w) float32, 'depth_test' (h,w) float32, 'extrinsics_train' (T,4,4),
+    'extrinsic_test' (4,4), 'intrinsics_train' (T,3,3), 'intrinsic_test' (3,3) or None [, 'depth_error_threshold', 'min_views']} --
+    the arguments of ``qa.visibility_mask``, which then computes the mask of the masked metrics on the device.
     Returns {'frames': [{'frame_num': ., metric: value rounded to 4 decimals, ...}], 'average': {metric: value}} with the
     reference's bookkeeping (``qa.summarise``) plus 'unrounded', the per-frame values before rounding.  With world_size > 1 each
     rank renders its block of every frame, rank 0 scores and the other ranks return None."""
@@ -196,6 +199,11 @@ def evaluate_frames(model, configs: dict, frames, device, rank: int = 0, world_s
             continue
         image, depth = ops.to_display(rendered[f'rgb{suffix}'].reshape(h * w, 3), rendered[f'depth{suffix}'].reshape(h * w))
         mask = on_device(frame['mask']) if frame.get('mask') is not None else None
+        if mask is None and frame.get('mask_views') is not None:
+            views = frame['mask_views']
+            mask = qa.visibility_mask(on_device(views['depth_train']), on_device(views['depth_test']), views['extrinsics_train'],
+                                      views['extrinsic_test'], views['intrinsics_train'], views.get('intrinsic_test'),
+                                      float(views.get('depth_error_threshold', 0.05)), int(views.get('min_views', 2)))
         row = {'frame_num': frame['frame_num']}
         row.update(qa.image_metrics(image.reshape(h, w, 3), on_device(frame['image']), mask))
         if frame.get('depth') is not None:

@@ -697,6 +697,103 @@ def rank_correlation_sums(x: Tensor, y: Tensor, sorted_x: Tensor, sorted_y: Tens
     return sums
 
 
+# ---------------------------------------------------------------------------------------------- Q2 visibility masks
+VISIBILITY_CAMERA = 30     # doubles per training view: inv(K_train) 3x3 | rows 0..2 of E_test inv(E_train) 3x4 | K_test 3x3
+
+_visibility_workspaces: Dict[torch.device, Tensor] = {}
+
+
+def _visibility_extent(views: int, h: int, w: int, name: str) -> int:
+    """Keys per view; refuses what the int32 keys cannot hold."""
+    per_view = (h + 1) * (w + 1) + 1
+    if views < 1 or h < 1 or w < 1 or views > 65535 or views * per_view >= 2 ** 31 - 1:
+        raise RuntimeError(f'{name}: {views} views of {h} x {w} are empty or exceed the int32 keys of the splat')
+    return per_view
+
+
+def visibility_mask_project(depth_train: Tensor, cameras: Tensor):
+    """Project every pixel of the (T,h,w) float32 training depths into the test view.  ``cameras``: float64 (T,30) on the device,
+    per view inv(K_train) | rows 0..2 of E_test inv(E_train) | K_test, row-major.  -> points float64 (T,3,h,w) (padded position
+    X, Y and transformed depth Z), keys int32 (T,h,w) (the list of every source), stats float64 (T,2) (max log-depth, max depth)."""
+    depth_train = _typed(depth_train, 'depth_train', (torch.float32,))
+    if depth_train.dim() != 3:
+        raise RuntimeError(f'depth_train: expected shape (views, h, w), got {tuple(depth_train.shape)}')
+    views, h, w = (int(s) for s in depth_train.shape)
+    _visibility_extent(views, h, w, 'depth_train')
+    cameras = _typed(cameras, 'cameras', (torch.float64,), (views, VISIBILITY_CAMERA))
+    dev = depth_train.device
+    points = torch.empty((views, 3, h, w), dtype=torch.float64, device=dev)
+    keys = torch.empty((views, h, w), dtype=torch.int32, device=dev)
+    stats = torch.empty((views, 2), dtype=torch.float64, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        need = int(lib.snerf_visibility_mask_workspace_bytes(views, h, w))
+        ws = _visibility_workspaces.get(dev)
+        if ws is None or ws.numel() < need:
+            ws = _visibility_workspaces[dev] = torch.empty((need,), dtype=torch.uint8, device=dev)
+        st = lib.snerf_visibility_mask_project(_ptr(depth_train), _ptr(cameras), views, h, w, _ptr(points), _ptr(keys), _ptr(stats),
+                                               _ptr(ws), _stream())
+    _lib.check(st, 'snerf_visibility_mask_project')
+    return points, keys, stats
+
+
+def visibility_mask_list_starts(sorted_keys: Tensor, views: int, h: int, w: int) -> Tensor:
+    """-> int32 (T * keys_per_view + 1) on the device: where the list of every key begins in the flat ascending ``sorted_keys``."""
+    views, h, w = int(views), int(h), int(w)
+    per_view = _visibility_extent(views, h, w, 'sorted_keys')
+    sorted_keys = _typed(sorted_keys, 'sorted_keys', (torch.int32,), (views * h * w,))
+    starts = torch.empty((views * per_view + 1,), dtype=torch.int32, device=sorted_keys.device)
+    lib = _lib.load()
+    with torch.cuda.device(sorted_keys.device):
+        st = lib.snerf_visibility_mask_list_starts(_ptr(sorted_keys), views, h, w, _ptr(starts), _stream())
+    _lib.check(st, 'snerf_visibility_mask_list_starts')
+    return starts
+
+
+def visibility_mask_gather(points: Tensor, order: Tensor, starts: Tensor, stats: Tensor, depth_test: Tensor,
+                           depth_error_threshold: float = 0.05, return_views: bool = False):
+    """Sum every test pixel's sources through the inverted index (``order``: the int64 permutation of the STABLE sort of the keys,
+    ``starts``: visibility_mask_list_starts) and apply the depth test.  -> uint8 (T,h,w) per-view masks; ``return_views``: also the
+    float64 (T,h,w) warped depths and weight sums."""
+    points = _typed(points, 'points', (torch.float64,))
+    if points.dim() != 4 or points.shape[1] != 3:
+        raise RuntimeError(f'points: expected shape (views, 3, h, w), got {tuple(points.shape)}')
+    views, h, w = int(points.shape[0]), int(points.shape[2]), int(points.shape[3])
+    per_view = _visibility_extent(views, h, w, 'points')
+    order = _typed(order, 'order', (torch.int64,), (views * h * w,))
+    starts = _typed(starts, 'starts', (torch.int32,), (views * per_view + 1,))
+    stats = _typed(stats, 'stats', (torch.float64,), (views, 2))
+    depth_test = _typed(depth_test, 'depth_test', (torch.float32,), (h, w))
+    dev = points.device
+    mask_views = torch.empty((views, h, w), dtype=torch.uint8, device=dev)
+    warped = torch.empty((views, h, w), dtype=torch.float64, device=dev) if return_views else None
+    weights = torch.empty((views, h, w), dtype=torch.float64, device=dev) if return_views else None
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        st = lib.snerf_visibility_mask_gather(_ptr(points), _ptr(order), _ptr(starts), _ptr(stats), _ptr(depth_test),
+                                              float(depth_error_threshold), views, h, w, _ptr(mask_views), _ptr(warped), _ptr(weights),
+                                              _stream())
+    _lib.check(st, 'snerf_visibility_mask_gather')
+    return (mask_views, warped, weights) if return_views else mask_views
+
+
+def visibility_mask_combine(mask_views: Tensor, min_views: int = 2) -> Tensor:
+    """-> bool (h,w) on the device: at least ``min_views`` of the uint8 / bool (T,h,w) per-view masks are set."""
+    mask_views = _typed(mask_views, 'mask_views', (torch.uint8, torch.bool))
+    if mask_views.dim() != 3:
+        raise RuntimeError(f'mask_views: expected shape (views, h, w), got {tuple(mask_views.shape)}')
+    views, h, w = (int(s) for s in mask_views.shape)
+    _visibility_extent(views, h, w, 'mask_views')
+    if not 1 <= int(min_views) <= views:
+        raise RuntimeError(f'min_views: expected 1..{views} (the number of training views), got {min_views}')
+    mask = torch.empty((h, w), dtype=torch.bool, device=mask_views.device)
+    lib = _lib.load()
+    with torch.cuda.device(mask_views.device):
+        st = lib.snerf_visibility_mask_combine(_ptr(mask_views), views, h, w, int(min_views), _ptr(mask), _stream())
+    _lib.check(st, 'snerf_visibility_mask_combine')
+    return mask
+
+
 # ---------------------------------------------------------------------------------------------- f1 losses
 class LossTermSpec:
     """One masked mean-squared-error term of the fused loss evaluation (struct snerf_loss_term).  ``two_sided``: the

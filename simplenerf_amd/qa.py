@@ -11,6 +11,9 @@ SSIM is pinned to a restatement of skimage's ``structural_similarity(gt, eval, m
 sigma=1.5, use_sample_covariance=False)`` on ``scipy.ndimage.gaussian_filter`` (tests/qa_reference.py), not to skimage itself.
 The reference's scripts round scaled fp32 depths to fp32 before subtracting; here the scale is applied in fp64 (a difference
 of ~1e-7, below their 4-decimal rounding).  LPIPS (04, 14) needs network weights and is not provided.
+
+The masks of the masked metrics are the stage's own first step (``src/qa/00_Common/src/mask_generators``): ``visibility_mask``
+splats the training views' depths into the test view and tests them against its depth, on the device (csrc/visibility_mask.hip).
 """
 from __future__ import annotations
 
@@ -113,6 +116,71 @@ def depth_metrics(eval_depth: Tensor, gt_depth: Tensor, eval_scale: float = 1.0,
                     'MaskedDepthMAE': float(_ratio(_ratio(sums[7], kept), median)),
                     'MaskedDepthSROCC': _correlation(None if masked_ranks is None else sums[11:14])})
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the masks of the masked metrics (the reference's src/qa/00_Common/src/mask_generators)
+def _matrices(value, name: str, shape) -> numpy.ndarray:
+    """A camera matrix argument (numpy or tensor, any float type) as float64 on the host, shape checked."""
+    if isinstance(value, torch.Tensor):
+        value = value.detach().cpu().numpy()
+    array = numpy.asarray(value)
+    if array.dtype.kind != 'f':
+        raise RuntimeError(f'{name}: expected a floating-point matrix, got {array.dtype}')
+    if array.shape != tuple(shape):
+        raise RuntimeError(f'{name}: expected shape {tuple(shape)}, got {array.shape}')
+    return array.astype(numpy.float64)
+
+
+def visibility_cameras(extrinsics_train, extrinsic_test, intrinsics_train, intrinsic_test=None) -> numpy.ndarray:
+    """The (T,30) float64 table ``ops.visibility_mask_project`` takes, inverted and composed on the host as the reference's
+    ``compute_transformed_points`` does: per view inv(K_train) | rows 0..2 of E_test inv(E_train) | K_test (the training view's own
+    intrinsic without ``intrinsic_test``).  Extrinsics are 4x4 world-to-camera, intrinsics 3x3."""
+    views = len(extrinsics_train)
+    e_train = _matrices(extrinsics_train, 'extrinsics_train', (views, 4, 4))
+    e_test = _matrices(extrinsic_test, 'extrinsic_test', (4, 4))
+    k_train = _matrices(intrinsics_train, 'intrinsics_train', (e_train.shape[0], 3, 3))
+    k_test = None if intrinsic_test is None else _matrices(intrinsic_test, 'intrinsic_test', (3, 3))
+    table = numpy.empty((e_train.shape[0], ops.VISIBILITY_CAMERA), dtype=numpy.float64)
+    for v in range(e_train.shape[0]):
+        table[v, 0:9] = numpy.linalg.inv(k_train[v]).reshape(-1)
+        table[v, 9:21] = numpy.matmul(e_test, numpy.linalg.inv(e_train[v]))[:3].reshape(-1)
+        table[v, 21:30] = (k_train[v] if k_test is None else k_test).reshape(-1)
+    return table
+
+
+def visibility_mask(depth_train: Tensor, depth_test: Tensor, extrinsics_train, extrinsic_test, intrinsics_train, intrinsic_test=None,
+                    depth_error_threshold: float = 0.05, min_views: int = 2, return_views: bool = False):
+    """The mask of the reference's masked metrics, computed on the device: a test pixel is visible from a training view when that
+    view's depth, splatted into the test view (``Warper.forward_warp``: bilinear proximity x depth weight 1 / exp(50 L / max L)),
+    lands on it and agrees with ``depth_test`` to ``depth_error_threshold`` x the view's largest depth (``MaskComputer.compute_mask``);
+    the mask holds where at least ``min_views`` training views see the pixel (the scripts' ``numpy.sum(masks, axis=0) > 1``).
+
+    ``depth_train`` float32 (T,h,w) and ``depth_test`` float32 (h,w) on the GPU, z-depths in the extrinsics' units (divide by the
+    scene's translation scale first, as the reference's script does); extrinsics (T,4,4) / (4,4) world-to-camera and intrinsics
+    (T,3,3) / (3,3), numpy or tensor -- without ``intrinsic_test`` every training view's own intrinsic is used.  Train and test views
+    share one resolution.  Returns the bool (h,w) mask on the device; ``return_views``: (mask, per-view masks bool (T,h,w), warped
+    depths float64 (T,h,w), weight sums float64 (T,h,w)).  Arithmetic is fp64 and free of atomics: the same input gives the same bits.
+    As in the reference a point behind the test camera still splats (with the largest depth weight) and no image is warped; a source
+    whose projection is not finite, and a view whose depths give max L = 0, add nothing (undefined in the reference)."""
+    depth_train = ops._typed(depth_train, 'depth_train', (torch.float32,))
+    if depth_train.dim() != 3 or depth_train.numel() < 1:
+        raise RuntimeError(f'depth_train: expected a non-empty shape (views, h, w), got {tuple(depth_train.shape)}')
+    views, h, w = (int(s) for s in depth_train.shape)
+    depth_test = ops._typed(depth_test, 'depth_test', (torch.float32,), (h, w))
+    if isinstance(min_views, bool) or int(min_views) != min_views or not 1 <= int(min_views) <= views:
+        raise RuntimeError(f'min_views: expected 1..{views} (the number of training views), got {min_views}')
+    if not float(depth_error_threshold) >= 0.0:
+        raise RuntimeError(f'depth_error_threshold: expected a non-negative number, got {depth_error_threshold}')
+    cameras = visibility_cameras(_matrices(extrinsics_train, 'extrinsics_train', (views, 4, 4)), extrinsic_test,
+                                 _matrices(intrinsics_train, 'intrinsics_train', (views, 3, 3)), intrinsic_test)
+    points, keys, stats = ops.visibility_mask_project(depth_train, torch.from_numpy(cameras).to(depth_train.device))
+    sorted_keys, order = torch.sort(keys.reshape(-1), stable=True)     # every list in ascending source order
+    starts = ops.visibility_mask_list_starts(sorted_keys, views, h, w)
+    gathered = ops.visibility_mask_gather(points, order, starts, stats, depth_test, depth_error_threshold, return_views)
+    mask_views = gathered[0] if return_views else gathered
+    mask = ops.visibility_mask_combine(mask_views, int(min_views))
+    return (mask, mask_views.bool(), gathered[1], gathered[2]) if return_views else mask
 
 
 # ---------------------------------------------------------------------------------------------------------------

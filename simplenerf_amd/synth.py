@@ -246,6 +246,26 @@ def synth_scene(seed: int = 0, num_views: int = 3, height: int = 48, width: int 
     }
 
 
+def extrinsic_of_pose(pose) -> numpy.ndarray:
+    """World-to-camera extrinsic [R t; 0 1] in the convention of the database's CameraExtrinsics.csv (x right, y DOWN, z FORWARD;
+    what ``qa.visibility_mask`` takes) from a processed camera-to-world pose as ``synth_scene`` and the data loader hold it
+    (x right, y UP, looking down -z): the inverse pose with the camera's y and z axes flipped, float64 (4,4).  With it a pixel
+    (x, y) at z-depth d -- ``true_depth``: the ray parameter of a ray with d_z = -1 -- is inv(K) (x, y, 1) d in camera space."""
+    flip = numpy.diag([1.0, -1.0, -1.0, 1.0])
+    return flip @ numpy.linalg.inv(numpy.asarray(pose, dtype=numpy.float64))
+
+
+def scene_mask_views(scene: dict, view: int) -> dict:
+    """The 'mask_views' entry of ``harness.evaluate_frames`` for view ``view`` of a ``synth_scene``: every OTHER view's true depth
+    is warped into it, and a pixel counts as visible when ``min(2, others)`` of them see it."""
+    others = [v for v in range(len(scene['poses'])) if v != view]
+    return {'depth_train': numpy.ascontiguousarray(scene['true_depth'][others]), 'depth_test': scene['true_depth'][view],
+            'extrinsics_train': numpy.stack([extrinsic_of_pose(scene['poses'][v]) for v in others]),
+            'extrinsic_test': extrinsic_of_pose(scene['poses'][view]),
+            'intrinsics_train': numpy.asarray(scene['intrinsics'], dtype=numpy.float64)[others],
+            'intrinsic_test': numpy.asarray(scene['intrinsics'][view], dtype=numpy.float64), 'min_views': min(2, len(others))}
+
+
 def loss_configs(iter_weighted: bool = True) -> list:
     """The nine losses every shipped experiment enables (src/NerfLlffTrainerTester01.py:351-430)."""
     late = {'iter_weights': {'0': 0, '10000': 0.1}} if iter_weighted else {'weight': 0.1}

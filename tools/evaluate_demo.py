@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """The reference's third stage on one MI355X: train the synthetic 3-view plane scene briefly (tools/train_demo.py), render every
 view, and score the frames on the device with ``harness.evaluate_frames`` -- RMSE / PSNR / SSIM of the 8-bit frame and
-RMSE / MAE / SROCC of the depth against the scene's true depth, per frame and averaged with the reference's rounding.
+RMSE / MAE / SROCC of the depth against the scene's true depth, plain and masked, per frame and averaged with the reference's
+rounding.  The masks are the reference's visibility masks, computed on the device from the other views' true depths and cameras
+(``qa.visibility_mask`` through the frames' 'mask_views').
     python tools/evaluate_demo.py [iterations]         (SNERF_PREC, SNERF_SEED as in tools/train_demo.py)"""
 import os
 import sys

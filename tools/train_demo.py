@@ -33,8 +33,10 @@ def camera_of(scene, view):
 
 def scene_frames(scene):
     """The scene's views as ``harness.evaluate_frames`` takes them: the 8-bit image the reference's post_process_image would
-    write (clip, round(255 x), uint8) and the true depth."""
+    write (clip, round(255 x), uint8), the true depth, and -- for the mask of the masked metrics -- the other views' true depths
+    and cameras (``synth.scene_mask_views``: the mask is computed on the device)."""
     return [{'frame_num': scene['frame_nums'][v], 'camera': camera_of(scene, v), 'depth': scene['true_depth'][v],
+             'mask_views': synth.scene_mask_views(scene, v),
              'image': numpy.round(numpy.clip(scene['images'][v], 0, 1) * 255).astype('uint8')} for v in range(len(scene['poses']))]
 
 
