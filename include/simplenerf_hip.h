@@ -476,6 +476,48 @@ int snerf_visibility_mask_combine(const unsigned char* mask_views, int views, in
                                   unsigned char* mask, snerf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Q3  LPIPS of a rendered frame on the device: lpips.LPIPS(net='alex'), version 0.1, lin layers on, eval mode, spatial=False, as
+ * the reference's src/qa/04_LPIPS and 14_MaskedLPIPS call it on the 8-bit frames.  Like Q1 and Q2 these were ADDED within ABI
+ * version 10 (no existing struct or signature changed; a caller checks that the symbol exists).  The library carries no weights:
+ * the caller passes torchvision's AlexNet convolutions and the package's lin layers, and snerf_lpips_pack re-orders them once.
+ *
+ *   x = u * 2 / 255 - 1 (fp32, in that order), (x - shift) / scale per channel; conv 3->64 k11 s4 p2 | pool, conv 64->192 k5 p2 |
+ *   pool, conv 192->384 k3 p1 | conv 384->256 k3 p1 | conv 256->256 k3 p1, every conv with bias and ReLU, pool = 3 x 3 stride 2
+ *   maximum without padding (floor mode); per layer l and pixel v = sum_c lin_l[c] (f_gt[c] / (|f_gt| + 1e-10) - f_eval[c] /
+ *   (|f_eval| + 1e-10))^2 over the post-ReLU features; LPIPS = sum_l mean over the layer's pixels of v.
+ *
+ * The convolutions run on the fp32 matrix cores as implicit GEMMs over NHWC activations; every sum (the k sum of an output
+ * element, the channel sums, the pixel sums) runs in one fixed order without atomics, so two calls on the same input return the
+ * same bits, and exchanging gt and eval does too.  The calls only enqueue on `stream`: no allocation, no synchronisation.
+ * height, width >= 31 (the smallest image the network accepts) and <= 16384.
+ */
+/* number of floats of the packed weight buffer */
+long long snerf_lpips_packed_floats(void);
+
+/* conv_weights  host array of 5 device pointers: (c_out, c_in, k, k) fp32, torch's layout (features.0/3/6/8/10.weight)
+ * conv_biases   host array of 5 device pointers: (c_out) fp32
+ * lin_weights   host array of 5 device pointers: (c_out) fp32 (lin{0..4}.model.1.weight, (1, c_out, 1, 1))
+ * scaling       host array of 6 floats, shift[3] then scale[3], or NULL for the package's (-.030, -.088, -.188) / (.458, .448, .450)
+ * packed        device, snerf_lpips_packed_floats() floats, written */
+int snerf_lpips_pack(const float* const* conv_weights, const float* const* conv_biases, const float* const* lin_weights,
+                     const float* scaling, float* packed, snerf_stream_t stream);
+
+/* bytes of device scratch snerf_lpips_sums needs for a height x width frame (0 for an extent it refuses); no initial state */
+long long snerf_lpips_workspace_bytes(int height, int width);
+
+/* extents of layer's (0..4) post-ReLU tap for a height x width frame */
+int snerf_lpips_tap_shape(int height, int width, int layer, int* tap_height, int* tap_width, int* channels);
+
+/* gt, eval  device (height, width, 3) uint8;  mask  device (height, width) bytes or NULL: eval is replaced by gt where it is zero
+ *           (14_MaskedLPIPS: an all-zero mask gives sums of exactly 0)
+ * packed    what snerf_lpips_pack wrote
+ * sums      device (5) fp64, written: per layer the sum of v over the tap's pixels; LPIPS = sum_l sums[l] / (tap_height_l tap_width_l)
+ * taps      NULL, or a host array of 5 device pointers (each may be NULL): layer l's post-ReLU activations of both images are
+ *           written there, fp32 (2, tap_height_l, tap_width_l, channels_l), gt first, channels last */
+int snerf_lpips_sums(const unsigned char* gt, const unsigned char* eval, const unsigned char* mask, int height, int width,
+                     const float* packed, double* sums, float* const* taps, void* workspace, snerf_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Opt-in event timing of the dominant kernels (the measurement row, SURVEY 8d: "achieved" of the roofline is measured
  * live with HIP events on the stream the kernel is launched on).  While enabled, every snerf_mlp_forward[_train] launch
  * (kind SNERF_PROFILE_MLP_FORWARD) and every snerf_mlp_backward call (SNERF_PROFILE_MLP_BACKWARD) -- also those issued

@@ -139,6 +139,12 @@ SIGNATURES = {
     'snerf_visibility_mask_gather': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, _FP, c_double, c_int, c_int, c_int, c_void_p,
                                              c_void_p, c_void_p, c_void_p]),
     'snerf_visibility_mask_combine': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    # LPIPS (Q3)
+    'snerf_lpips_packed_floats': (c_longlong, []),
+    'snerf_lpips_pack': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'snerf_lpips_workspace_bytes': (c_longlong, [c_int, c_int]),
+    'snerf_lpips_tap_shape': (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    'snerf_lpips_sums': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # include/simplenerf_train.h
     'snerf_loss_workspace_bytes': (c_longlong, []),
     'snerf_loss_forward': (c_int, [POINTER(LossTerm), c_int, c_int, c_longlong, _FP, _FP, c_void_p, c_void_p]),

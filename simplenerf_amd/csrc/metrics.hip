@@ -12,6 +12,7 @@
 #include <cmath>
 #include <type_traits>
 
+#include "block_reduce.h"
 #include "metrics_tile.h"
 #include "snerf_common.h"
 
@@ -19,30 +20,10 @@ namespace {
 
 using namespace snerf::ssim_tile;
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
+using namespace snerf::reduce;          // kBlock, kWaves, wave_sum_t, block_sum (shared with csrc/lpips.hip)
+
 constexpr int kMaxPartials = 1024;   // workgroups of a 1-D reduction
 constexpr int kMaxSums = 4;          // values per workgroup of a 1-D reduction
-
-template <typename T>
-__device__ __forceinline__ T wave_sum_t(T v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// Sum of `v` over the workgroup's kBlock threads, valid in thread 0.  `lds` holds kWaves values; reusable after the call.
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* lds) {
-    v = wave_sum_t(v);
-    __syncthreads();   // (the previous use of `lds` has been read)
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    T s = lds[0];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) s += lds[w];
-    return s;
-}
 
 // Second launch of every reduction: ONE workgroup; out[j] = sum over b of partials[b * width + j], thread t taking b = t,
 // t + kBlock, ... in order, then block_sum.  `sorted` (depth sums only): also out[width] = numpy.median of sorted * scale.

@@ -169,7 +169,7 @@ def predict_frame(model, configs: dict, camera: dict, device, rank: int = 0, wor
 
 @torch.no_grad()
 def evaluate_frames(model, configs: dict, frames, device, rank: int = 0, world_size: int = 1, ray_block: int = 65536,
-                    collective: Optional[bool] = None) -> Optional[dict]:
+                    collective: Optional[bool] = None, lpips_weights=None) -> Optional[dict]:
     """The reference's QA stage over a test set (src/qa/*), without the frames leaving the device: every frame is rendered
     through the path of ``predict_frame``, converted for display there (uint8 colour, depth clipped at 0) and scored against its
     targets by ``qa.image_metrics`` / ``qa.depth_metrics`` -- only the metrics' scalar sums cross to the host.
@@ -179,6 +179,7 @@ def evaluate_frames(model, configs: dict, frames, device, rank: int = 0, world_s
     frame may carry 'mask_views': {'depth_train' (T,h,w) float32, 'depth_test' (h,w) float32, 'extrinsics_train' (T,4,4),
     'extrinsic_test' (4,4), 'intrinsics_train' (T,3,3), 'intrinsic_test' (3,3) or None [, 'depth_error_threshold', 'min_views']} --
     the arguments of ``qa.visibility_mask``, which then computes the mask of the masked metrics on the device.
+    ``lpips_weights``: a ``qa.LpipsWeights``; every row then also carries LPIPS (and MaskedLPIPS where there is a mask).
     Returns {'frames': [{'frame_num': ., metric: value rounded to 4 decimals, ...}], 'average': {metric: value}} with the
     reference's bookkeeping (``qa.summarise``) plus 'unrounded', the per-frame values before rounding.  With world_size > 1 each
     rank renders its block of every frame, rank 0 scores and the other ranks return None."""
@@ -206,6 +207,8 @@ def evaluate_frames(model, configs: dict, frames, device, rank: int = 0, world_s
                                       float(views.get('depth_error_threshold', 0.05)), int(views.get('min_views', 2)))
         row = {'frame_num': frame['frame_num']}
         row.update(qa.image_metrics(image.reshape(h, w, 3), on_device(frame['image']), mask))
+        if lpips_weights is not None:
+            row.update(qa.lpips_metrics(image.reshape(h, w, 3), on_device(frame['image']), lpips_weights, mask))
         if frame.get('depth') is not None:
             row.update(qa.depth_metrics(depth.reshape(h, w), on_device(frame['depth']),
                                         float(frame.get('depth_scale', 1.0)), float(frame.get('gt_depth_scale', 1.0)), mask))

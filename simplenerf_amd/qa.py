@@ -10,7 +10,13 @@ ranks) and mask compaction are torch calls on the device.
 SSIM is pinned to a restatement of skimage's ``structural_similarity(gt, eval, multichannel=True, gaussian_weights=True,
 sigma=1.5, use_sample_covariance=False)`` on ``scipy.ndimage.gaussian_filter`` (tests/qa_reference.py), not to skimage itself.
 The reference's scripts round scaled fp32 depths to fp32 before subtracting; here the scale is applied in fp64 (a difference
-of ~1e-7, below their 4-decimal rounding).  LPIPS (04, 14) needs network weights and is not provided.
+of ~1e-7, below their 4-decimal rounding).
+
+LPIPS (04, 14) is ``lpips.LPIPS(net='alex')`` on the device (csrc/lpips.hip: the five AlexNet convolutions as implicit GEMMs on
+the fp32 matrix cores, fixed-order fp64 layer sums).  The build carries no network weights: ``LpipsWeights`` takes them from the
+caller's checkpoint files (torchvision's AlexNet + the package's ``alex.pth``, or a saved ``lpips.LPIPS`` state dict), read with
+``torch.load(weights_only=True)`` -- neither package has to be installed.  The metric is pinned to tests/lpips_reference.py, a
+restatement of the package's published definition.
 
 The masks of the masked metrics are the stage's own first step (``src/qa/00_Common/src/mask_generators``): ``visibility_mask``
 splats the training views' depths into the test view and tests them against its depth, on the device (csrc/visibility_mask.hip).
@@ -181,6 +187,106 @@ def visibility_mask(depth_train: Tensor, depth_test: Tensor, extrinsics_train, e
     mask_views = gathered[0] if return_views else gathered
     mask = ops.visibility_mask_combine(mask_views, int(min_views))
     return (mask, mask_views.bool(), gathered[1], gathered[2]) if return_views else mask
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# LPIPS (the reference's src/qa/04_LPIPS, 14_MaskedLPIPS: lpips.LPIPS(net='alex') on the 8-bit frames)
+LPIPS_SHIFT, LPIPS_SCALE = (-.030, -.088, -.188), (.458, .448, .450)      # the package's ScalingLayer buffers
+_LPIPS_CONV_KEYS = {'lpips': ('net.slice1.0', 'net.slice2.3', 'net.slice3.6', 'net.slice4.8', 'net.slice5.10'),
+                    'torchvision': ('features.0', 'features.3', 'features.6', 'features.8', 'features.10')}
+
+
+def lpips_tensors(state_dict, lin_state_dict=None) -> Dict[str, object]:
+    """The 15 tensors of LPIPS-alex and the scaling layer's buffers out of checkpoint dictionaries, identified by name:
+    {'conv_weights': [5], 'conv_biases': [5], 'lin_weights': [5] as (c_out,), 'shift': (3,), 'scale': (3,)}, float32 on the host.
+
+    ``state_dict``: a saved ``lpips.LPIPS(net='alex').state_dict()`` (``net.slice{1..5}.{0,3,6,8,10}.*``, ``lin{k}.model.1.weight``,
+    ``scaling_layer.*``) or torchvision's AlexNet (``features.{0,3,6,8,10}.*``; classifier keys are ignored).  ``lin_state_dict``: the
+    package's ``alex.pth`` (``lin{k}.model.1.weight`` only), needed with torchvision's file and overriding otherwise.  A missing or
+    mis-shaped tensor raises with its key; ``scaling_layer.shift`` / ``.scale``, where present, replace the package's constants."""
+    for name, value in (('state_dict', state_dict), ('lin_state_dict', lin_state_dict)):
+        if not (value is None and name == 'lin_state_dict') and not hasattr(value, 'keys'):
+            raise RuntimeError(f'{name}: expected a dictionary of tensors (a state dict), got {type(value).__name__}')
+    layout = next((name for name, keys in _LPIPS_CONV_KEYS.items() if any(k.startswith(keys[0] + '.') for k in state_dict.keys())), None)
+    if layout is None:
+        raise RuntimeError("state_dict: neither a saved lpips.LPIPS(net='alex') state dict (no key 'net.slice1.0.weight') nor "
+                           "torchvision's AlexNet (no key 'features.0.weight')")
+
+    def take(source, key, shape):
+        if key not in source:
+            raise RuntimeError(f'{key}: missing from the checkpoint')
+        value = source[key]
+        if not isinstance(value, torch.Tensor) or tuple(value.shape) != tuple(shape):
+            got = tuple(value.shape) if isinstance(value, torch.Tensor) else type(value).__name__
+            raise RuntimeError(f'{key}: expected a tensor of shape {tuple(shape)}, got {got}')
+        return value.detach().to('cpu', torch.float32).contiguous()
+
+    out: Dict[str, object] = {'conv_weights': [], 'conv_biases': [], 'lin_weights': []}
+    for l, (c_out, c_in, k) in enumerate(ops.LPIPS_CONVS):
+        prefix = _LPIPS_CONV_KEYS[layout][l]
+        out['conv_weights'].append(take(state_dict, prefix + '.weight', (c_out, c_in, k, k)))
+        out['conv_biases'].append(take(state_dict, prefix + '.bias', (c_out,)))
+        lin_key = f'lin{l}.model.1.weight'
+        lin_source = lin_state_dict if lin_state_dict is not None else state_dict
+        if lin_key not in lin_source and f'lins.{l}.model.1.weight' in lin_source:
+            lin_key = f'lins.{l}.model.1.weight'
+        out['lin_weights'].append(take(lin_source, lin_key, (1, c_out, 1, 1)).reshape(c_out))
+    for name, default in (('shift', LPIPS_SHIFT), ('scale', LPIPS_SCALE)):
+        key = f'scaling_layer.{name}'
+        if key in state_dict:
+            value = state_dict[key]
+            if not isinstance(value, torch.Tensor) or value.numel() != 3:
+                got = tuple(value.shape) if isinstance(value, torch.Tensor) else type(value).__name__
+                raise RuntimeError(f'{key}: expected a tensor of 3 values, got {got}')
+            out[name] = value.detach().to('cpu', torch.float32).reshape(3)
+        else:
+            out[name] = torch.tensor(default, dtype=torch.float32)
+    return out
+
+
+class LpipsWeights:
+    """The weights of LPIPS-alex, packed once for the device kernels (``ops.lpips_pack``); pass it to ``lpips_metrics`` /
+    ``harness.evaluate_frames(lpips_weights=...)``.  ``tensors``: what ``lpips_tensors`` returned."""
+
+    def __init__(self, tensors: Dict[str, object], device='cuda'):
+        self.device = torch.device(device)
+        if self.device.type == 'cuda' and self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        move = lambda group: [t.to(self.device) for t in group]
+        self.packed = ops.lpips_pack(move(tensors['conv_weights']), move(tensors['conv_biases']), move(tensors['lin_weights']),
+                                     tensors['shift'], tensors['scale'])
+
+    @classmethod
+    def from_state_dict(cls, state_dict, lin_state_dict=None, device='cuda') -> 'LpipsWeights':
+        return cls(lpips_tensors(state_dict, lin_state_dict), device)
+
+    @classmethod
+    def load(cls, path, lin_path=None, device='cuda') -> 'LpipsWeights':
+        """``path``: torchvision's AlexNet checkpoint (then ``lin_path`` is the package's ``alex.pth``) or a saved
+        ``lpips.LPIPS(net='alex').state_dict()``; plain ``torch.save``d dictionaries of tensors, read with ``weights_only=True``."""
+        state = torch.load(path, map_location='cpu', weights_only=True)
+        lin_state = None if lin_path is None else torch.load(lin_path, map_location='cpu', weights_only=True)
+        return cls.from_state_dict(state, lin_state, device)
+
+
+def lpips_metrics(eval_image: Tensor, gt_image: Tensor, weights: LpipsWeights, mask: Optional[Tensor] = None) -> Dict[str, float]:
+    """LPIPS (AlexNet, version 0.1) of a uint8 (h,w,3) frame against its ground truth, both on the GPU; with a bool (h,w) ``mask``
+    also MaskedLPIPS, the score of (gt, where(mask, eval, gt)) -- exactly 0 for an all-false mask, as in the reference."""
+    gt, image, mask, h, w = ops._image_pair(gt_image, eval_image, mask)
+    if min(h, w) < ops.LPIPS_MIN_EXTENT:
+        raise RuntimeError(f'gt_image: AlexNet needs {ops.LPIPS_MIN_EXTENT} pixels on every side, the image extent is {h} x {w}')
+    if not isinstance(weights, LpipsWeights):
+        raise RuntimeError(f'weights: expected qa.LpipsWeights, got {type(weights).__name__}')
+    sums = ops.lpips_sums(gt, image, weights.packed)
+    if mask is not None:
+        sums = torch.cat([sums, ops.lpips_sums(gt, image, weights.packed, mask)])
+    sums = sums.cpu().numpy()                                   # 5 or 10 scalars cross to the host
+    pixels = [th * tw for th, tw, _ in ops.lpips_tap_shapes(h, w)]
+    score = lambda layer_sums: float(sum(numpy.float64(s) / n for s, n in zip(layer_sums, pixels)))
+    out = {'LPIPS': score(sums[:5])}
+    if mask is not None:
+        out['MaskedLPIPS'] = score(sums[5:])
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------
