@@ -19,10 +19,8 @@ OBJ_DIR = os.path.join(CSRC, 'build')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 # -ffp-contract=off: the elementwise stages must round exactly like the reference's separate torch/numpy ops;
 # fused multiply-adds are written explicitly (fmaf) where they are wanted.
-# -include probe_guard.h: every translation unit refuses to compile with a diagnostic switch defined unless SNERF_PROBE_BUILD is
-# defined too (see that header).
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt', '-Wall', '-Wno-unused-function', '-Wno-inline-asm',
-         f'-I{INCLUDE}', '-include', os.path.join(CSRC, 'probe_guard.h')]
+         f'-I{INCLUDE}']
 # Files of small fp32 kernels that run BESIDE the MLP kernels when the levels of a pass go side by side (render.hip), built without the
 # SLP vectoriser: it packs neighbouring scalar fp32 operations into v_pk_*_f32 and, when a shared factor sits in the odd register
 # of a pair, selects it with op_sel:[0,1] -- the one operand selection that miscomputes beside another kernel's MFMAs on MI355X
@@ -30,34 +28,6 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=o
 FILE_FLAGS = {'composite': ['-fno-slp-vectorize'], 'losses': ['-fno-slp-vectorize']}
 OBJDUMP = os.environ.get('LLVM_OBJDUMP', '/opt/rocm/lib/llvm/bin/llvm-objdump')
 HAZARDOUS_PACKED_FORM = r'v_pk_\w+_f32 .*op_sel:\[0,1'     # low result <- HIGH register of the second source
-DIAGNOSTIC_PREFIXES = ('SNERF_ABL_', 'SNERF_PROBE_', 'SNERF_CLOCK_STAMP')
-# where a stray -D can come from besides ``extra_flags``: the compiler command itself and the variables hipcc / clang append
-FLAG_ENVIRONMENT = ('HIPCC', 'HIPCC_COMPILE_FLAGS_APPEND', 'HIPCC_LINK_FLAGS_APPEND', 'HIP_CLANG_FLAGS', 'CXXFLAGS', 'CPPFLAGS', 'CFLAGS',
-                    'CCC_OVERRIDE_OPTIONS')
-
-
-def diagnostic_switches(extra_flags=(), environ=None):
-    """Diagnostic macros (ablations / probes: wrong results by design) that would reach the compiler: [(where, text)]."""
-    environ = os.environ if environ is None else environ
-    found = [('extra_flags', f) for f in extra_flags if any(p in f for p in DIAGNOSTIC_PREFIXES)]
-    for name in FLAG_ENVIRONMENT:
-        value = environ.get(name, '')
-        if any(p in value for p in DIAGNOSTIC_PREFIXES):
-            found.append((name, value))
-    return found
-
-
-def check_shipped_build(extra_flags, output, environ=None):
-    """The shipped library (``output`` == LIB) is built with FLAGS alone: refuse any diagnostic switch, wherever it comes from.
-    A variant must carry -DSNERF_PROBE_BUILD and another output name (tools/probes/build_variant.py does both)."""
-    found = diagnostic_switches(extra_flags, environ)
-    if os.path.abspath(output) == os.path.abspath(LIB):
-        if found:
-            raise RuntimeError('refusing to build the shipped library with diagnostic switches (they produce wrong results by design): '
-                               + '; '.join(f'{where}: {text}' for where, text in found)
-                               + ' -- use tools/probes/build_variant.py, which writes gpurun_abl_<name>.so')
-    elif found and not any('SNERF_PROBE_BUILD' in f for f in extra_flags):
-        raise RuntimeError('a diagnostic variant must be built with -DSNERF_PROBE_BUILD (tools/probes/build_variant.py adds it)')
 
 
 def _sources():
@@ -77,25 +47,16 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build_library(force: bool = False, verbose: bool = False, extra_flags=(), output: str = LIB, obj_dir: str = OBJ_DIR, only=()) -> str:
-    """``extra_flags`` / ``output`` / ``obj_dir``: diagnostic variants (tools/probes/build_variant.py) -- the shipped library is
-    always built with FLAGS alone.  ``only``: source stems a variant compiles with its flags; every other object is linked from
-    the shipped build's object directory (which must be current)."""
-    check_shipped_build(extra_flags, output)
-    if only and os.path.abspath(output) == os.path.abspath(LIB):
-        raise RuntimeError('`only` is for diagnostic variants')
-    os.makedirs(obj_dir, exist_ok=True)
+def build_library(force: bool = False, verbose: bool = False) -> str:
+    os.makedirs(OBJ_DIR, exist_ok=True)
     headers = _headers()
     jobs = []
     objs = []
     for src in _sources():
-        if only and src[:-4] not in only:
-            objs.append(os.path.join(OBJ_DIR, src[:-4] + '.o'))
-            continue
-        obj = os.path.join(obj_dir, src[:-4] + '.o')
+        obj = os.path.join(OBJ_DIR, src[:-4] + '.o')
         objs.append(obj)
         if force or _stale(obj, [os.path.join(CSRC, src)] + headers):
-            jobs.append([HIPCC, *FLAGS, *FILE_FLAGS.get(src[:-4], []), *extra_flags, '-c', os.path.join(CSRC, src), '-o', obj])
+            jobs.append([HIPCC, *FLAGS, *FILE_FLAGS.get(src[:-4], []), '-c', os.path.join(CSRC, src), '-o', obj])
 
     def run(cmd):
         if verbose:
@@ -113,15 +74,15 @@ def build_library(force: bool = False, verbose: bool = False, extra_flags=(), ou
         jobs.sort(key=lambda cmd: next((i for i, name in enumerate(heavy) if name in cmd[-3]), len(heavy)))
         with ThreadPoolExecutor(max_workers=min(os.cpu_count() or 4, 8, len(jobs))) as pool:
             list(pool.map(run, jobs))
-    if jobs or force or _stale(output, objs):
-        run([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', *objs, '-o', output])
-        found = hazardous_packed_forms(output)
-        if found and os.path.abspath(output) == os.path.abspath(LIB):
-            os.remove(output)
+    if jobs or force or _stale(LIB, objs):
+        run([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', *objs, '-o', LIB])
+        found = hazardous_packed_forms(LIB)
+        if found:
+            os.remove(LIB)
             raise RuntimeError('the built library contains packed fp32 instructions with the operand selection that miscomputes beside '
                                'MFMA kernels on MI355X (see opaque_pair() in csrc/mlp_device.h):\n'
                                + '\n'.join(f'  {kernel}: {text}' for kernel, text in found[:20]))
-    return output
+    return LIB
 
 
 def hazardous_packed_forms(library: str):

@@ -22,7 +22,6 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "clock_stamp.h"
 #include "mlp_device_f16.h"
 
 namespace snerf {
@@ -534,18 +533,9 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
-SNERF_STAMP_DEFINE(wgrad16)
-
 constexpr int kPairBytes = 2304;   // LDS image of one 32-row tile: piece 0 at +0, piece 1 at +1152 (bank phase +32 dwords:
 constexpr int kPieceGap = 1152;    // the two 16-lane groups of a half-wave read different pieces of the same tile)
-constexpr int kWgrad16Buffers = 3;
-#if defined(SNERF_PROBE_RING4)  // ablation: a fourth slot for the 8-bit instance (measured: +0.23 ms per config-5 iteration)
-constexpr int wgrad16_ring(bool x8, bool) { return x8 ? 4 : kWgrad16Buffers; }
-#elif defined(SNERF_PROBE_SMALL_RING)   // ablation: that many slots for the small-job launch (4: 107 -> 138 us, 5: 140 us)
-constexpr int wgrad16_ring(bool, bool partial) { return partial ? SNERF_PROBE_SMALL_RING : kWgrad16Buffers; }
-#else
-constexpr int wgrad16_ring(bool, bool) { return kWgrad16Buffers; }
-#endif
+constexpr int kWgrad16Buffers = 3;  // (a fourth ring slot for the 8-bit instance measured +0.23 ms per config-5 iteration)
 
 // PARTIAL: the small head / encoding jobs -- (8 x 2), (1 x 8), (4 x 1) and (1 x 4) tiles for the main MLP -- share ONE launch
 // of the <2, 2> instance: a wave's register tile may then be only partly covered by the job (wave-uniform guards around its
@@ -622,9 +612,6 @@ __global__ void __launch_bounds__(256, 1) wgrad16_kernel(JobTable table, const u
             if (q < dy_pieces_real) {
                 src = reinterpret_cast<const char*>(grads + ((b0 * job.grad_rows + job.dy_row0) * 32 + q * 512));
                 stride = (long long)job.grad_rows * 64;
-#ifdef SNERF_PROBE_HALF_DY     // traffic ablation (WRONG results): every second dY piece of a wide operand comes from the zero page
-                if (job.out_tiles >= 4 && (q & 1)) { src = reinterpret_cast<const char*>(zeros + 192); stride = 0; }
-#endif
             }
         } else if (!x8 && job.x2_tiles > 0 && q - pieces_dy >= 2 * (job.in_tiles - job.x2_tiles)) {
             // the rider's X tiles (WgradJob::x2_row0): whole encoding tiles
@@ -635,9 +622,6 @@ __global__ void __launch_bounds__(256, 1) wgrad16_kernel(JobTable table, const u
             // (8-bit tile images are one KiB each, packed: WgradJob::x_row0 already counts them so)
             src = reinterpret_cast<const char*>(acts + ((b0 * job.act_rows + job.x_row0) * 32 + (q - pieces_dy) * 512));
             stride = (long long)job.act_rows * 64;
-#ifdef SNERF_PROBE_HALF_X      // traffic ablation (WRONG results): every second X piece of a wide operand comes from the zero page
-            if (job.in_tiles >= 4 && ((q - pieces_dy) & 1)) { src = reinterpret_cast<const char*>(zeros + 192); stride = 0; }
-#endif
         }
         piece_src[k] = src;
         piece_stride[k] = stride;
@@ -742,7 +726,6 @@ __global__ void __launch_bounds__(256, 1) wgrad16_kernel(JobTable table, const u
     };
 
     const int nblocks = (int)(b1 - b0);
-    SNERF_STAMP_BEGIN();
     FragSet even, odd;
     int stage_slot = 0, read_slot = 0;                       // ring positions of the next block to request / to read
     // RING slots, AHEAD blocks requested before the first is used.  What the large class is bound by (config 5, round 4;
@@ -750,18 +733,15 @@ __global__ void __launch_bounds__(256, 1) wgrad16_kernel(JobTable table, const u
     // this addressing (244 us + the launch's fixed costs: ramp, 64 MiB of partial sums at the end = the measured 260); 8-bit X,
     // 24-KiB blocks -- one wave's chain of LDS-read latency and 32 MFMAs per block, ~1.1 us (215 us + fixed costs = 237), not
     // its bytes (181 us).  More blocks in flight are neutral in the skeleton and LOSE in this kernel: a fourth slot
-    // (SNERF_PROBE_RING4) 256-260 us, the same three slots refilled one barrier earlier (SNERF_PROBE_DEEP) 243 us (255 for
-    // 16-bit X), the small-job launch 107 -> 138 us with a fourth or fifth slot (SNERF_PROBE_SMALL_RING).  Not explained.
-    constexpr int RING = wgrad16_ring(X8, PARTIAL);
+    // 256-260 us, the same three slots refilled one barrier earlier 243 us (255 for 16-bit X), the small-job launch
+    // 107 -> 138 us with a fourth slot (140 with a fifth).  Not explained.
+    constexpr int RING = kWgrad16Buffers;
     constexpr bool OVERLAP = !PARTIAL && NO * NI >= 8;       // (the schedule below)
     // The serial schedule reads block n's second k-step after the mid-block barrier, so block n's slot cannot be refilled
     // there: AHEAD = RING - 1.  In the overlapped schedule every read of block n has LANDED before that barrier (they are
-    // waited for inside the first k-step), so the barrier would free block n's own slot: the probe requests one block more.
-#ifdef SNERF_PROBE_DEEP
-    constexpr int AHEAD = OVERLAP ? RING : RING - 1;
-#else
+    // waited for inside the first k-step), so the barrier would free block n's own slot: requesting one block more there
+    // is the "refilled one barrier earlier" form measured above.
     constexpr int AHEAD = RING - 1;
-#endif
     auto advance = [](int& slot) { slot = slot == RING - 1 ? 0 : slot + 1; };
     auto first_block = [&]() {
         const int ahead = nblocks < AHEAD ? nblocks : AHEAD;
@@ -875,10 +855,6 @@ __global__ void __launch_bounds__(256, 1) wgrad16_kernel(JobTable table, const u
                     request(odd, read_slot, 1);
                 }
             }
-#ifdef SNERF_PROBE_WGRAD_NOMATH      // ablation (WRONG results): the block stream alone -- requests, waits and barriers, no LDS reads, no MFMAs
-            for (int n = 0; n + 1 < nblocks; ++n) { advance(read_slot); next_block(n); }
-            return;
-#endif
             for (int n = 0; n + 1 < nblocks; ++n) {
                 if (active) step(even, ah_even, odd, ah_odd, std::true_type{});
                 advance(read_slot);
@@ -917,7 +893,6 @@ __global__ void __launch_bounds__(256, 1) wgrad16_kernel(JobTable table, const u
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (NO == 2 && NI == 8) SNERF_STAMP_END(wgrad16);      // (the large class)
     if (!active) return;
     const int in_cols = job.in_tiles * 32;
     // 8-bit X: accumulator column n = (lane half hh = n >> 4, byte b = n & 15 of the slot) is feature 16 (b >> 3) + 8 ((b >> 2) & 1) + 4 hh + (b & 3)
@@ -1021,18 +996,13 @@ __global__ void __launch_bounds__(256) reduce_kernel(JobTable table, const float
 
 // Workgroups (= partial sums the reduction folds afterwards) of a small head / encoding job.  Every chunk ends with a partial
 // of out_tiles x in_tiles x 4 KiB that is written once and read once, so the count trades staging parallelism against
-// partial-sum traffic (the two 8x2-tile encoding jobs of the main MLP: 64 KB per chunk).  -DSNERF_SMALL_CHUNKS=n for A/B builds.
+// partial-sum traffic (the two 8x2-tile encoding jobs of the main MLP: 64 KB per chunk).
 // 512 dated from one launch per register-tile class (one job per launch); with the four or five small jobs of an MLP in ONE launch
 // it left a workgroup 8 blocks of a 64-samples-per-ray pass to stream and a 64 KB partial to write: config-5 backward per
 // iteration 5.05 ms (384), 4.85 (256), 4.85 (128), 4.94 (64) against 5.25-5.49 at 512, same box; blocks / 32 clamped to
 // 64 .. 384 measured the same as a fixed 192.
-#ifndef SNERF_SMALL_CHUNKS
-#define SNERF_SMALL_CHUNKS 192
-#endif
-#ifndef SNERF_MID_BLOCKS
-#define SNERF_MID_BLOCKS 32
-#endif
-constexpr int kSmallJobChunks = SNERF_SMALL_CHUNKS;
+constexpr int kSmallJobChunks = 192;
+constexpr int kMidBlocks = 32;      // (blocks of operands per workgroup of a lone mid-sized job: chunk planning below)
 
 // Register tile (NO, NI) per wave for a job of (out_tiles x in_tiles): the 4 waves must cover it as a WO x WI grid.
 inline void wave_tile(const WgradJob& j, int* no, int* ni) {
@@ -1140,12 +1110,9 @@ Workspace plan_workspace(const snerf::MlpPlan& p, long long total_samples, bool 
     // counts scaled with rows").  Every workgroup ends with a 256 KB partial that is written once and read back by the reduction
     // whatever it contracted over: one rank's share of a strong-scaled batch (256-512 rows x 64 samples = 512-1024 blocks) paid the
     // full 64 MiB + reduction per level for 1/8 of the operands, and its levels run side by side (render.hip), so the CUs a level
-    // leaves are not idle.  SNERF_LARGE_MIN_BLOCKS for A/B builds (0 = the fixed 256 of rounds 3-4).
-#ifndef SNERF_LARGE_MIN_BLOCKS
-#define SNERF_LARGE_MIN_BLOCKS 16
-#endif
-    const long long large_budget = SNERF_LARGE_MIN_BLOCKS > 0
-        ? std::min<long long>(256, std::max<long long>(64, blocks / SNERF_LARGE_MIN_BLOCKS)) : 256;
+    // leaves are not idle.  (Rounds 3-4 had a fixed 256.)
+    constexpr int kLargeMinBlocks = 16;
+    const long long large_budget = std::min<long long>(256, std::max<long long>(64, blocks / kLargeMinBlocks));
     for (WgradJob& j : w.jobs) {
         int no, ni;
         wave_tile(j, &no, &ni);
@@ -1156,7 +1123,7 @@ Workspace plan_workspace(const snerf::MlpPlan& p, long long total_samples, bool 
             // was feature_linear, whose X (h_D) stays 16-bit, 260 us, however fast the seven fp8 jobs ran
             long long peers_weight = 0;
             // (measured with in-kernel stamps, config 5, two boxes: a block of 24 KiB costs its workgroup 0.76 / 0.87 of what
-            // one of 32 KiB does -- tools/probes/wgrad_wg_times.py; 0.80 here)
+            // one of 32 KiB does -- profiles/r04_wgrad_wg_times.txt; 0.80 here)
             auto weight = [](const WgradJob& k) { return 20 * k.out_tiles + (k.x8 ? 12 : 20) * k.in_tiles; };
             for (const WgradJob& k : w.jobs) {
                 int ko, ki;
@@ -1165,19 +1132,17 @@ Workspace plan_workspace(const snerf::MlpPlan& p, long long total_samples, bool 
             }
             chunks = large_budget * weight(j) / peers_weight;   // rounded DOWN: 7 jobs x 37 chunks = 259 workgroups ran as 256 + a second round of 3
             // (a lone job of fewer than 64 tile products -- the views layer's 4 x 9 -- ends every workgroup with a 144 KB
-            // partial: at least SNERF_MID_BLOCKS blocks of operands per workgroup; config 5: 128 instead of 256 workgroups
+            // partial: at least kMidBlocks blocks of operands per workgroup; config 5: 128 instead of 256 workgroups
             // for a 64-samples-per-ray pass is worth 0.04 ms per iteration, 64 costs 0.25)
             // (round 5: ... but never fewer than 64 workgroups while a workgroup still gets four blocks -- one rank's share of a
             // strong-scaled batch, 256 rays x 64 samples = 512 blocks, left this job on 16 CUs: 33 us per launch for 0.3 us of
             // operand traffic, profiles/r05_train_share_512_kernel_stats.csv)
-            if (j.out_tiles * j.in_tiles < 64 && chunks > blocks / SNERF_MID_BLOCKS)
-                chunks = std::min(chunks, std::max<long long>({blocks / SNERF_MID_BLOCKS, std::min<long long>(64, blocks / 4), 1}));
+            if (j.out_tiles * j.in_tiles < 64 && chunks > blocks / kMidBlocks)
+                chunks = std::min(chunks, std::max<long long>({blocks / kMidBlocks, std::min<long long>(64, blocks / 4), 1}));
             cap = blocks / 8;
         } else {
-#ifndef SNERF_SMALL_CHUNKS_FP32
-#define SNERF_SMALL_CHUNKS_FP32 256      // (512 -> 256: config-5 backward 29.06 -> 28.88 ms in fp32, 13.10 -> 13.02 in f16x3)
-#endif
-            chunks = f16 ? kSmallJobChunks : SNERF_SMALL_CHUNKS_FP32;     // (fp32 / f16x3: one launch per register-tile class, one or two jobs each)
+            constexpr int kSmallJobChunksFp32 = 256;     // (512 -> 256: config-5 backward 29.06 -> 28.88 ms in fp32, 13.10 -> 13.02 in f16x3)
+            chunks = f16 ? kSmallJobChunks : kSmallJobChunksFp32;     // (fp32 / f16x3: one launch per register-tile class, one or two jobs each)
             cap = blocks / 8;
         }
         if (chunks > cap) chunks = cap;
@@ -1260,10 +1225,10 @@ template <int NO, int NI, bool PARTIAL = false, bool BF = false, bool X8 = false
 int launch_wgrad16(const JobTable& table, const float* grads, const float* acts, float* partial, hipStream_t stream) {
     int max_tiles = 0;
     for (int j = 0; j < table.count; ++j) max_tiles = std::max(max_tiles, table.jobs[j].out_tiles + table.jobs[j].in_tiles);
-    const size_t lds_bytes = (size_t)wgrad16_ring(X8, PARTIAL) * max_tiles * kPairBytes;
+    const size_t lds_bytes = (size_t)kWgrad16Buffers * max_tiles * kPairBytes;
     auto kernel = wgrad16_kernel<NO, NI, PARTIAL, BF, X8>;
     static snerf::DeviceOnce configured;   // per device: the attribute belongs to (kernel, device)
-    const int attr = snerf::raise_dynamic_lds(configured, reinterpret_cast<const void*>(kernel), wgrad16_ring(X8, PARTIAL) * (PARTIAL ? 10 : 16) * kPairBytes, "mlp_backward");
+    const int attr = snerf::raise_dynamic_lds(configured, reinterpret_cast<const void*>(kernel), kWgrad16Buffers * (PARTIAL ? 10 : 16) * kPairBytes, "mlp_backward");
     if (attr != SNERF_OK) return attr;
     hipLaunchKernelGGL(kernel, dim3((unsigned)table.wg_start[table.count]), dim3(256), lds_bytes, stream, table,
                        reinterpret_cast<const unsigned short*>(grads), reinterpret_cast<const unsigned short*>(acts), partial,
@@ -1396,9 +1361,6 @@ extern "C" int snerf_mlp_backward(const snerf_mlp_desc* desc, const float* packe
     static const int classes[][2] = {{2, 8}, {2, 2}, {2, 1}, {1, 9}, {1, 8}, {1, 4}, {1, 2}, {1, 1}};   // ({1, 9}: 16-bit modes only)
     // 16-bit mode: every small job (fewer than 32 tile products: heads, encodings) rides in ONE launch of the <2, 2> instance
     // with partial register tiles (wgrad16_kernel PARTIAL) instead of one launch per register-tile class
-#ifdef SNERF_PROBE_NO_SMALL_FOLD     // A/B probe builds: one launch per register-tile class, as before round 3
-    auto small16 = [&](const WgradJob&) { return false; };
-#else
     // ... provided the four waves of that instance COVER the job: wave (wo, wi) of a wgrid_o x wgrid_i grid owns out tiles
     // [2 wo, 2 wo + 2) x in tiles [2 wi, 2 wi + 2) (wgrad16_kernel: wgrid_i = max(in_tiles / 2, 1)); a shape they do not
     // cover (3 in-tiles, 16 x 1, ...) goes to its own register-tile class below instead of silently losing tiles
@@ -1409,7 +1371,6 @@ extern "C" int snerf_mlp_backward(const snerf_mlp_desc* desc, const float* packe
         const int wgrid_o = 4 / wgrid_i;
         return wgrid_i * 2 >= job.in_tiles && wgrid_o * 2 >= job.out_tiles;
     };
-#endif
     if (f16) {
         JobTable sub;
         sub.count = 0;

@@ -14,21 +14,11 @@
 #include <algorithm>
 #include <type_traits>
 
-// timing ablations of this kernel alone (tools/probes/build_variant.py; wrong results): no weight DMA / no workgroup barrier
-#ifdef SNERF_ABL_CHAIN_NODMA
-#define SNERF_ABL_NODMA
-#endif
-#ifdef SNERF_ABL_CHAIN_NOBARRIER
-#define SNERF_ABL_NOBARRIER
-#endif
 #pragma once
-#include "clock_stamp.h"
 #include "mlp_device_f16.h"
 #include "mlp_plan.h"
 
 namespace {
-
-SNERF_STAMP_DEFINE(chain_f16)
 
 struct HalfChainArgs {
     ChainArgs c;
@@ -122,9 +112,6 @@ __device__ __forceinline__ void store_dy(const f32x16 (&acc)[U], float* __restri
         for (int u = 0; u < U; ++u)
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-#ifdef SNERF_PROBE_HALF_DY     // traffic ablation (tools/probes/build_variant.py; WRONG results): the bytes an fp8 dY tile would take
-                if (s == 1) continue;
-#endif
                 bf16x8 v;
 #pragma unroll
                 for (int e = 0; e < 8; e += 2) {
@@ -171,7 +158,6 @@ __global__ void __launch_bounds__(chain_waves(P, VIEWDEP, DEPTH) * 64, chain_wav
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int half = lane >> 5;
-    SNERF_STAMP_BEGIN();
     constexpr int HK = WT * 2;   // k-steps over a full-width dY
     constexpr int VK = VT * 2;   // k-steps over the views layer's dY
 
@@ -342,9 +328,6 @@ __global__ void __launch_bounds__(chain_waves(P, VIEWDEP, DEPTH) * 64, chain_wav
         int gback_exp = exponent_of(gback), fnext_exp = 0;
         bf16x8 stage;
         auto epilogue_pair = [&](int t, int pr, int row0, const unsigned (&words)[WT / 2]) __attribute__((always_inline)) {
-#ifdef SNERF_ABL_CHAIN_NOEPI     // timing ablation (tools/probes/build_variant.py): no epilogue work at all -- wrong results
-            return;
-#endif
             const int r = 2 * pr, b0 = 16 * (t & 1) + r;
             const float x = keep_if_bit_2op(acc[t][r], words[t >> 1], b0);
             const float y = keep_if_bit_2op(acc[t][r + 1], words[t >> 1], b0 + 1);
@@ -356,15 +339,7 @@ __global__ void __launch_bounds__(chain_waves(P, VIEWDEP, DEPTH) * 64, chain_wav
             // shadow of an MFMA -- r03_mfma_valu_shadow.txt; 571 -> 534 us per fine-size call, gradients bit-identical)
             const bf16x2 q = __builtin_convertvector(f32x2{__builtin_ldexpf(x, gback_exp), __builtin_ldexpf(y, gback_exp)}, bf16x2);
             stage[r & 7] = q[0]; stage[(r & 7) + 1] = q[1];
-#ifdef SNERF_ABL_CHAIN_NOSTORE   // timing ablation: the epilogue's arithmetic, but nothing written
-            if (pr == 7 && t == 0 && stage[0] == (__bf16)123.0f)
-#else
-            if ((pr & 3) == 3
-#ifdef SNERF_PROBE_HALF_DY
-                && pr == 3
-#endif
-                )   // eight values staged: one 16-byte store (read once, by the weight-gradient kernel)
-#endif
+            if ((pr & 3) == 3)   // eight values staged: one 16-byte store (read once, by the weight-gradient kernel)
             {
                 __builtin_nontemporal_store(stage, reinterpret_cast<bf16x8*>(rows16 + (long long)row0 * 32 + (2 * t + (pr >> 2)) * 512 + slot8));
                 st.note_vmem(1);
@@ -462,7 +437,6 @@ __global__ void __launch_bounds__(chain_waves(P, VIEWDEP, DEPTH) * 64, chain_wav
     }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    SNERF_STAMP_END(chain_f16);
 }
 
 template <int WT, int VT, bool VIEWDEP, int P, int DEPTH = 0, bool BF = false>

@@ -123,10 +123,6 @@ struct UnitStreamT {
     // pieces (a few times per pass).  `issued` feeds the counted vmcnt of the next acquire().  (A select-free variant that
     // keeps reading the stream into the rest of the slot saves a third of the scalar instructions and measured 1 % slower.)
     __device__ __forceinline__ void fetch_piece() {
-#ifdef SNERF_ABL_NODMA
-        pend_left -= pend_left > 0 ? 1 : 0;
-        return;
-#endif
         const int adv = pend_left > 0 ? NW * 256 : 0;
         pend_off += adv * 4; pend_dst += adv;
         if constexpr (P == 1) {
@@ -209,20 +205,13 @@ struct UnitStreamT {
         // (the generic 64-way dispatch compiles to a compare-and-branch tree of ~30 scalar instructions, and with one wave
         // per SIMD every instruction is an issue slot: the steady-state counts of the 256-wide trunk -- the successor's
         // k/2 resp. k/4 DMA instructions and nothing else -- are tested first)
-#ifdef SNERF_PROBE_NO_VMWAIT
-        // timing probe (wrong results): the DMA is issued but nobody waits for it -- what the waits cost, as against the issue
-        (void)allowed;
-#else
         // (... times the D - 2 units that stay in flight)
         constexpr int kSteady = (D - 2) * (P == 3 ? 8 : 16 / NW);
         if (D <= 4 && allowed == kSteady) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kSteady) : "memory");
         else wait_vmcnt(allowed);
-#endif
         younger = 0;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // my LDS reads of unit i-1 are complete
-#ifndef SNERF_ABL_NOBARRIER
         __builtin_amdgcn_s_barrier();
-#endif
         const float* ready = lds + slot * slot_floats;
         const int vacated = slot == 0 ? D - 1 : slot - 1;
         if (next2 > 0) begin_fetch(next2, vacated); else issued_next_none();
@@ -270,9 +259,6 @@ struct TileSplitter {
     bool on;
     __device__ __forceinline__ void step(int i) const {  // i = 0..7 (compile-time after unrolling)
         if (!on) return;
-#ifdef SNERF_ABL_NOSPLIT
-        if (i > 0) return;
-#endif
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             const int r = 2 * i + e;
@@ -443,10 +429,6 @@ __device__ __forceinline__ void convert_tile(const f32x16& acc, f16x8& h0, f16x8
 // (ReLU and) split one finished accumulator tile into the two k-steps it feeds in the next layer.
 template <bool RELU>
 __device__ __forceinline__ void split_tile(const f32x16& acc, f16x8& h0, f16x8& l0, f16x8& h1, f16x8& l1) {
-#ifdef SNERF_ABL_NOCONVERT
-    h0[0] = (_Float16)acc[0]; l0[0] = (_Float16)acc[1]; h1[0] = (_Float16)acc[8]; l1[0] = (_Float16)acc[9];
-    return;
-#endif
     // two values at a time, so that each conversion is one packed instruction (v_cvt_pk_f16_f32, round to nearest even)
     // and the halves land in adjacent lanes of the fragment without separate packing moves
 #pragma unroll
@@ -555,9 +537,6 @@ __device__ __forceinline__ void store_pieces(const f16x8 (&frag)[NB], _Float16* 
     // non-temporal: the saved tensors (GBs per pass) are read back only by the backward kernels, long after they have left
     // every cache; the plain store policy cost the storing forward 7 % and the backward 9 % (r02, A/B builds)
     for (int s = 0; s < NKS; ++s) {
-#ifdef SNERF_PROBE_HALF_X      // traffic ablation (tools/probes/build_variant.py; WRONG results): the bytes an fp8 X tile would take
-        if (NKS >= 8 && (s & 1)) continue;
-#endif
         __builtin_nontemporal_store(frag[s], reinterpret_cast<f16x8*>(rows + s * 512 + slot * 8));
     }
 }

@@ -140,11 +140,9 @@ static int forward_impl(const snerf_mlp_desc* desc, const float* packed, const f
     snerf::ProfileScope timed(SNERF_PROFILE_MLP_FORWARD, s, a.total);
     if (precision != SNERF_PRECISION_FP32 && !train) {
         // rendering with the fp16 modes: the 16x16x32 MFMA layout where it is built (more work per joule)
-        // (A/B probes build with -DSNERF_PROBE_NO_M16; no run-time switch decides which kernel renders)
-#ifndef SNERF_PROBE_NO_M16
+        // (no run-time switch decides which kernel renders)
         const int st16 = snerf::mlp_forward_m16(plan, a, precision == SNERF_PRECISION_F16X3 ? 3 : 1, s, bf16);
         if (st16 != -1) return st16;
-#endif
     }
     if (precision == SNERF_PRECISION_F16X3) return snerf::mlp_forward_f16x3(plan, a, train, 3, s);
     if (precision == SNERF_PRECISION_F16 || bf16 || precision == SNERF_PRECISION_F16S8) {

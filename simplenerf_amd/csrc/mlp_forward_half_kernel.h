@@ -22,13 +22,10 @@
 #include <type_traits>
 
 #pragma once
-#include "clock_stamp.h"
 #include "mlp_device_f16.h"
 #include "mlp_plan.h"
 
 namespace {
-
-SNERF_STAMP_DEFINE(forward_f16)
 
 // f(integral_constant<I>), ..., f(integral_constant<N-1>): one inlined copy of the body per index (a `#pragma unroll` on a
 // loop this large is refused by the optimiser)
@@ -103,7 +100,6 @@ __global__ void __launch_bounds__(P == 1 ? 512 : 256, P == 1 ? 2 : 1) mlp_forwar
     for (int i = threadIdx.x * 4; i < args.const_floats; i += NW * 64 * 4)
         *reinterpret_cast<f32x4*>(consts + i) = *reinterpret_cast<const f32x4*>(a.packed + a.bias_offset + i);
     __syncthreads();
-    SNERF_STAMP_BEGIN();
 
     const long long first = ((long long)blockIdx.x * NW + wave) * 32 + (lane & 31);
     const bool live = first < a.total;
@@ -287,7 +283,6 @@ __global__ void __launch_bounds__(P == 1 ? 512 : 256, P == 1 ? 2 : 1) mlp_forwar
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (!BF) watch.report(a.range_flag, a.weight_range);
-    SNERF_STAMP_END(forward_f16);
     if (live && half == 0) {
         a.sigma[first] = sigma;
         a.rgb[first * 3 + 0] = rgb[0];

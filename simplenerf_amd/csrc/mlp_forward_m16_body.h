@@ -4,7 +4,6 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "clock_stamp.h"
 #include "mlp_device_f16.h"
 
 namespace {
@@ -17,8 +16,6 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
-SNERF_STAMP_DEFINE(forward_m16)
-
 struct M16Args {
     MlpArgs m;
     long long stream_offset;   // MlpPlan::m16_offset
@@ -30,7 +27,7 @@ typedef f32x4 Tile16[2][2];   // [row half][sample half]
 
 // Ring slots of the weight stream.  The single-product kernels (two waves per SIMD on one ring) run THREE units ahead since
 // round 5 -- measured neutral (0.278 against 0.281 ms per 262 144 samples: a build that never waits for its DMA is no faster
-// either, what costs 14 % is ISSUING it; tools/probes/m16_ablation.py, profiles/r05_m16_ablation.txt) and kept for what it
+// either, what costs 14 % is ISSUING it; profiles/r05_m16_ablation.txt) and kept for what it
 // frees: the encodings' hand-over scratch (48 KiB, dead after the prologue) now lies in slots three and four, 124 instead of
 // 148 KiB of LDS per workgroup.
 __host__ __device__ constexpr int m16_ring(int products) { return products == 1 ? 4 : 3; }
@@ -210,23 +207,6 @@ __device__ __forceinline__ void mlp_forward_m16_body(const M16Args& args, long l
     // the lanes that need them through a 6-KiB LDS scratch per wave ----------------------------------------------------------
     f16x8 pe_h[2][2], pe_l[2][2], pev_h[1][2], pev_l[1][2];
     const long long wave_base = (block * NW + wave) * 32;
-#ifdef SNERF_PROBE_M16_NOENCODE
-    // timing probe (wrong results): the operands of the encodings are lane-dependent constants -- no positions, no sin / cos, no
-    // hand-over through LDS: what the 861-instruction prologue costs a pass
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                pe_h[c][s][j] = (_Float16)(0.01f * ((lane * 7 + c * 3 + s + j) & 63) - 0.3f);
-                pe_l[c][s][j] = (_Float16)0.0f;
-            }
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { pev_h[0][s][j] = (_Float16)(0.02f * ((lane + s + j) & 31) - 0.3f); pev_l[0][s][j] = (_Float16)0.0f; }
-#else
     {
         const int i32 = lane & 31, half = lane >> 5;
         const long long total = TILE ? tile.total : a.total;
@@ -239,11 +219,7 @@ __device__ __forceinline__ void mlp_forward_m16_body(const M16Args& args, long l
 #pragma unroll
         for (int k = 0; k < 3; ++k) v[k] = a.view_dirs[ray * 3 + k];
         float pe[snerf::kPointsKSteps], pev[snerf::kViewsKSteps];
-#ifdef SNERF_PROBE_M16_UNPAIRED     // A/B build: the encoding as before the opaque pair (contains the hazardous packed form)
-        constexpr bool kPaired = false;
-#else
         constexpr bool kPaired = true;     // (see opaque_pair, mlp_device.h)
-#endif
         encode<snerf::kPointsPairs, snerf::kPointsKSteps, kPaired>(x, half, pe);
         encode<snerf::kViewsPairs, snerf::kViewsKSteps, kPaired>(v, half, pev);
         // register 8ks + j of lane half h = position p = 16 (ks & 1) + 8h + j of k-block ks / 2 -> lane group (p & 15) / 4,
@@ -298,13 +274,11 @@ __device__ __forceinline__ void mlp_forward_m16_body(const M16Args& args, long l
             for (int s = 0; s < 2; ++s) pev_l[0][s] = frags[(4 + s) * 64];
         }
     }
-#endif
     __syncthreads();   // consts visible; every wave is done with the scratch before the DMA is given its slots
     if constexpr (RING > 3) {      // the rest of the initial run-ahead, now that the scratch is free
 #pragma unroll
         for (int u = 2; u < RING - 1; ++u) st.start_more(u, ks_of(u));
     }
-    SNERF_STAMP_BEGIN();
 
     const float* bias = consts;
     const float* wout = consts + (a.pts_out_w - a.bias_offset);
@@ -374,7 +348,6 @@ __device__ __forceinline__ void mlp_forward_m16_body(const M16Args& args, long l
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (a wave never ends with LDS-DMA in flight)
     if constexpr (!BF) watch.report(a.range_flag, a.weight_range);
-    SNERF_STAMP_END(forward_m16);
 
     // ---- outputs: the four lane groups hold partial sums over their rows ----------------------------------------------------
 #pragma unroll

@@ -123,13 +123,11 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(GemmArgs g) {
     // XCDs and A comes from HBM once per n tile (4 x at width 512).  When the m tiles divide by eight, XCD x takes the row blocks
     // congruent to x and walks their n tiles one after the other: A's rows are fetched once and hit in that XCD's L2 afterwards.
     int tile_m = blockIdx.y, tile_n = blockIdx.x;
-#ifndef SNERF_PROBE_GEMM_PLAIN_ORDER
     if ((gridDim.y & 7u) == 0) {
         const unsigned linear = blockIdx.y * gridDim.x + blockIdx.x, xcd = linear & 7u, idx = linear >> 3;
         tile_m = (int)((idx / gridDim.x) * 8u + xcd);
         tile_n = (int)(idx % gridDim.x);
     }
-#endif
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const long long k_lo = g.split_stride ? (long long)blockIdx.z * g.k_chunk : 0;
     const long long k_hi = g.split_stride ? (k_lo + g.k_chunk < g.K ? k_lo + g.k_chunk : g.K) : g.K;
@@ -165,10 +163,6 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(GemmArgs g) {
         // WHEN IT IS STORED, after this stage's MFMAs (a predicated load per element compiles to one exec-masked basic block per
         // load, and a select right here makes the MFMAs wait for the loads they are meant to hide)
         a_inside = b_inside = 0;
-#ifdef SNERF_PROBE_GEMM_NOLOAD       // timing ablation (wrong results): nothing fetched from memory
-        (void)a_stage; (void)b_stage; (void)k_left;
-        return;
-#endif
 #pragma unroll
         for (int e = 0; e < LA; ++e) {
             const bool inside = a_m + e * a_dm < m_left && a_k + e * a_dk < k_left;
@@ -186,9 +180,6 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(GemmArgs g) {
     float* const bs0 = &Bs[0][b_k][b_n];
     const int as_step = a_dk * (BM + kPad) + a_dm, bs_step = b_dk * (BN + kPad) + b_dn;
     auto store_stage = [&](int buf) {
-#ifdef SNERF_PROBE_GEMM_NOSTORE      // timing ablation (wrong results): nothing staged into LDS
-        return;
-#endif
 #pragma unroll
         for (int e = 0; e < LA; ++e) as0[buf * (kBK * (BM + kPad)) + e * as_step] = (a_inside >> e) & 1u ? ra[e] : 0.0f;
 #pragma unroll
@@ -231,17 +222,13 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(GemmArgs g) {
 #pragma unroll
                     for (int tn = 0; tn < TN; ++tn) bv[(p + 1) & 1][tn] = b_rd[2 * (p + 1) * (BN + kPad) + 32 * tn];
                 }
-#ifndef SNERF_PROBE_GEMM_NO_PREFETCH
                 __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
                 for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
                     for (int tn = 0; tn < TN; ++tn)
                         acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[p & 1][tm], bv[p & 1][tn], acc[tm][tn], 0, 0, 0);
-#ifndef SNERF_PROBE_GEMM_NO_PREFETCH
                 __builtin_amdgcn_sched_barrier(0);
-#endif
             }
             if (more) {
                 store_stage(buf ^ 1);
@@ -305,10 +292,6 @@ struct Stager {
     __device__ __forceinline__ void load(long long k_first, int k_left) {
         const char* stage = tile + k_first * sk_bytes;
         inside = 0;
-#ifdef SNERF_PROBE_GEMM_NOLOAD       // timing ablation (wrong results): nothing fetched from memory
-        (void)stage; (void)k_left;
-        return;
-#endif
 #pragma unroll
         for (int e = 0; e < kGroups; ++e) {
             const bool in = t0 + e * dt < left && k0 + e * dk < k_left;      // (sizes are multiples of four: all four or none)
@@ -319,9 +302,6 @@ struct Stager {
         }
     }
     __device__ __forceinline__ void store(float* buffer) {
-#ifdef SNERF_PROBE_GEMM_NOSTORE      // timing ablation (wrong results): nothing staged into LDS
-        return;
-#endif
         if constexpr (MODE == 1) {
 #pragma unroll
             for (int e = 0; e < kGroups; ++e)
@@ -365,13 +345,11 @@ __global__ void __launch_bounds__(256, 2) gemm_vec_kernel(GemmArgs g) {
     const unsigned tiles_n = (unsigned)((g.N + BN - 1) / BN), tiles_m = (unsigned)((g.M + BM - 1) / BM), tiles = tiles_n * tiles_m;
     auto tile_of = [&](unsigned linear_id, int* m_first, int* n_first) {
         unsigned tile_m = linear_id / tiles_n, tile_n = linear_id % tiles_n;
-#ifndef SNERF_PROBE_GEMM_PLAIN_ORDER
         if ((tiles_m & 7u) == 0) {
             const unsigned xcd = linear_id & 7u, idx = linear_id >> 3;
             tile_m = (idx / tiles_n) * 8u + xcd;
             tile_n = idx % tiles_n;
         }
-#endif
         *m_first = (int)tile_m * BM;
         *n_first = (int)tile_n * BN;
     };
@@ -439,17 +417,13 @@ __global__ void __launch_bounds__(256, 2) gemm_vec_kernel(GemmArgs g) {
     #pragma unroll
                         for (int tn = 0; tn < TN; ++tn) bv[(p + 1) & 1][tn] = b_rd[2 * (p + 1) * SB + 32 * tn];
                     }
-    #ifndef SNERF_PROBE_GEMM_NO_PREFETCH
                     __builtin_amdgcn_sched_barrier(0);
-    #endif
     #pragma unroll
                     for (int tm = 0; tm < TM; ++tm)
     #pragma unroll
                         for (int tn = 0; tn < TN; ++tn)
                             acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[p & 1][tm], bv[p & 1][tn], acc[tm][tn], 0, 0, 0);
-    #ifndef SNERF_PROBE_GEMM_NO_PREFETCH
                     __builtin_amdgcn_sched_barrier(0);
-    #endif
                 }
                 if (more) {
                     store_stage(buf ^ 1);
@@ -534,9 +508,6 @@ int launch_gemm(const GemmArgs& g, int splits, hipStream_t s) {
         const bool a_along_m = g.a_rs == 1 && g.a_cs % 4 == 0 && aligned16(g.A) && g.M % 4 == 0;
         const bool b_along_k = g.b_rs == 1 && g.b_cs % 4 == 0 && aligned16(g.B) && k_fours;
         const bool b_along_n = g.b_cs == 1 && g.b_rs % 4 == 0 && aligned16(g.B) && g.N % 4 == 0;
-#ifdef SNERF_PROBE_GEMM_SCALAR_STAGING
-        hipLaunchKernelGGL((gemm_kernel<128, 128>), grid, dim3(256), 0, s, g);
-#else
         // (persistent workgroups: two per CU of the current device, a multiple of eight so that a workgroup's tiles stay on its XCD)
         const unsigned tiles = grid.x * grid.y;
         const dim3 walkers(tiles < persistent_workgroups() ? tiles : persistent_workgroups(), 1, grid.z);
@@ -544,7 +515,6 @@ int launch_gemm(const GemmArgs& g, int splits, hipStream_t s) {
         else if (a_along_k && b_along_n) hipLaunchKernelGGL((gemm_vec_kernel<128, 128, 1, 2>), walkers, dim3(256), 0, s, g);
         else if (a_along_m && b_along_n) hipLaunchKernelGGL((gemm_vec_kernel<128, 128, 2, 2>), walkers, dim3(256), 0, s, g);
         else hipLaunchKernelGGL((gemm_kernel<128, 128>), grid, dim3(256), 0, s, g);
-#endif
     } else {
         hipLaunchKernelGGL((gemm_kernel<64, 64>), grid, dim3(256), 0, s, g);
     }

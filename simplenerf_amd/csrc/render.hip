@@ -41,10 +41,7 @@ struct Marching {
 // between their calls.  Above the threshold every CU is
 // busy with one level and the levels stay on the caller's stream, in order (two backward calls side by side measured the same
 // as back to back there: DESIGN_LOG 12.4).
-#ifndef SNERF_SIDE_BY_SIDE_SAMPLES          // (A/B builds: -DSNERF_SIDE_BY_SIDE_SAMPLES=n)
-#define SNERF_SIDE_BY_SIDE_SAMPLES 65536
-#endif
-constexpr long long kSideBySideSamples = SNERF_SIDE_BY_SIDE_SAMPLES;
+constexpr long long kSideBySideSamples = 65536;
 constexpr int kSideStreams = 3;
 
 struct SideStreams {
@@ -101,9 +98,6 @@ int join_streams(SideStreams* s, hipStream_t main, int count) {
 }
 
 bool side_by_side(const snerf_render_config* cfg, const snerf_render_mlp* mlps, long long num_rays) {
-#ifdef SNERF_PROBE_NO_SIDE_BY_SIDE
-    return false;      // A/B builds (tools/probes/share_ab.py)
-#endif
     if (num_rays * cfg->num_coarse > kSideBySideSamples) return false;
     int levels = 0;
     for (int l = 0; l < SNERF_RENDER_LEVELS; ++l) levels += mlps[l].desc ? 1 : 0;
@@ -177,12 +171,8 @@ extern "C" int snerf_render_forward(const snerf_render_config* cfg, const snerf_
     float* coarse_weights = out->level[0].weights;
     // the main coarse level of a model with a fine pass: compositing and resampling in ONE kernel, the ray's weights handed
     // over in LDS (no predict_visibility on that level: its visibility2 compositing reads the weights from memory)
-#ifdef SNERF_PROBE_NO_K4K5_FUSION
-    const bool fuse_resample = false;
-#else
     const bool fuse_resample = fine && !rays->depths_fine && !mlps[0].desc->predict_visibility && cfg->num_coarse >= 3 &&
                                sizeof(float) * 4 * (size_t)(2 * cfg->num_coarse + cfg->num_fine + 2 * (cfg->num_coarse - 1)) <= 64 * 1024;
-#endif
     if (fine && !rays->depths_fine && !coarse_weights && !fuse_resample) {
         SNERF_REQUIRE(workspace, "render_forward: workspace is required (main coarse weights feed the resampling)");
         coarse_weights = workspace;

@@ -495,43 +495,17 @@ def test_bench_strong_scaling_rows(monkeypatch):
     assert '256 pixel + 256' in bench.train_workload(512, 8, True) and '4096-row batch over 8' in bench.train_workload(512, 8, True)
 
 
-def test_every_diagnostic_switch_is_guarded():
-    """the ablation / probe switches inside the product kernels (wrong results by design) cannot reach the shipped
-    library.  (i) every such macro the sources test is listed in csrc/probe_guard.h, which is force-included into every
-    translation unit and #errors unless SNERF_PROBE_BUILD is defined; (ii) build.py refuses them for the shipped library's name
-    wherever they come from (extra flags, HIPCC, HIPCC_COMPILE_FLAGS_APPEND, CXXFLAGS ...); (iii) a real compile of a library
-    source with -DSNERF_PROBE_HALF_X fails, and passes once SNERF_PROBE_BUILD is there too."""
-    import subprocess
+def test_no_diagnostic_switch_is_left_in_the_kernels():
+    """VERDICT r4 #6, the strong form: the product kernels hold no ablation / probe switch and no clock stamp any more (wrong
+    results by design; their measurements are recorded under profiles/), so there is nothing left to guard -- and the build
+    force-includes no guard header."""
     from simplenerf_amd import build
-    csrc = build.CSRC
-    guard = open(os.path.join(csrc, 'probe_guard.h')).read()
-    used = set()
-    for name in os.listdir(csrc):
-        if name.endswith(('.hip', '.h')) and name != 'probe_guard.h':
-            used |= set(re.findall(r'\b(SNERF_(?:ABL|PROBE)_[A-Z0-9_]+|SNERF_CLOCK_STAMP)\b', open(os.path.join(csrc, name)).read()))
-    used.discard('SNERF_PROBE_BUILD')
-    assert used and all(f'defined({m})' in guard for m in used), sorted(m for m in used if f'defined({m})' not in guard)
-    assert '-include' in build.FLAGS and build.FLAGS[build.FLAGS.index('-include') + 1].endswith('probe_guard.h')
-    # (ii)
-    with pytest.raises(RuntimeError, match='refusing to build the shipped library'):
-        build.check_shipped_build(['-DSNERF_PROBE_HALF_X'], build.LIB, environ={})
-    for var in ('HIPCC', 'HIPCC_COMPILE_FLAGS_APPEND', 'CXXFLAGS'):
-        with pytest.raises(RuntimeError, match=var):
-            build.check_shipped_build([], build.LIB, environ={var: '/opt/rocm/bin/hipcc -DSNERF_ABL_NODMA'})
-    with pytest.raises(RuntimeError, match='SNERF_PROBE_BUILD'):
-        build.check_shipped_build(['-DSNERF_PROBE_HALF_X'], '/tmp/variant.so', environ={})
-    build.check_shipped_build(['-DSNERF_PROBE_BUILD', '-DSNERF_PROBE_HALF_X'], '/tmp/variant.so', environ={})
-    build.check_shipped_build([], build.LIB, environ={'CXXFLAGS': '-O2'})
-    with pytest.raises(RuntimeError, match='refusing'):
-        build.build_library(extra_flags=['-DSNERF_PROBE_HALF_X'])
-    # (iii) the compiler itself (host pass only: seconds)
-    source = os.path.join(csrc, 'display.hip')
-    cmd = [build.HIPCC, *build.FLAGS, '--cuda-host-only', '-fsyntax-only', source]
-    bad = subprocess.run(cmd + ['-DSNERF_PROBE_HALF_X'], capture_output=True, text=True, timeout=300)
-    assert bad.returncode != 0 and 'diagnostic switch' in bad.stderr, bad.stderr[-2000:]
-    for extra in ([], ['-DSNERF_PROBE_HALF_X', '-DSNERF_PROBE_BUILD']):
-        ok = subprocess.run(cmd + extra, capture_output=True, text=True, timeout=300)
-        assert ok.returncode == 0, ok.stderr[-2000:]
+    switch = re.compile(r'SNERF_(ABL|PROBE)_[A-Z0-9_]+|SNERF_CLOCK_STAMP|SNERF_STAMP_')
+    sources = [name for name in os.listdir(build.CSRC) if name.endswith(('.hip', '.h'))]
+    assert sources
+    left = {name: sorted({m.group(0) for m in switch.finditer(open(os.path.join(build.CSRC, name)).read())}) for name in sources}
+    assert not any(left.values()), {name: found for name, found in left.items() if found}
+    assert '-include' not in build.FLAGS
 
 
 def test_no_packed_fp32_instruction_reads_the_high_register_into_the_low_result(tmp_path):

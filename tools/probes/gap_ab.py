@@ -5,14 +5,12 @@ Three ways of issuing the SAME step (1024 rays, 128+128, eval) on one GPU, in on
   events   eager, the library's timing events around every MLP launch (what bench.py times: ~5.7 us of idle per event pair)
   plain    eager, no events: kernels back to back in the queue
   graph    the whole step captured once as a HIP graph and replayed (no host work between kernels at all)
-For each arm: wall time per step over `steps` steps (median of `rounds` rounds), and -- when the library is the
--DSNERF_CLOCK_STAMP diagnostic build (tools/probes/build_variant.py clock -DSNERF_CLOCK_STAMP) -- the clock the chip held
-INSIDE the fused MLP kernel during that arm: median over workgroups of d(s_memtime) / d(s_memrealtime) x 100 MHz
-(MI355X_MICROARCH.md, DVFS give-back 6; sysfs clocks read up to 10 % high).
+For each arm: wall time per step over `steps` steps (median of `rounds` rounds).  (The records of round 3,
+profiles/r03_gap_ab_box*.jsonl, also hold the clock the chip held INSIDE the fused MLP kernel, from a build with in-kernel clock
+stamps that the library no longer has.)
 
     python tools/probes/gap_ab.py [f16|f16x3|fp32] [lib.so]        -> one JSON object per line
 """
-import ctypes
 import json
 import os
 import statistics
@@ -32,8 +30,7 @@ from simplenerf_amd import harness, ops, synth  # noqa: E402
 
 dev = torch.device('cuda', 0)
 torch.cuda.set_device(dev)
-lib = _lib.load()
-stamped = hasattr(lib, 'snerf_debug_clock_stamps_forward_m16')
+_lib.load()
 configs = synth.make_configs('headline')
 camera = synth.camera('fern', 0)
 h, w = camera['resolution']
@@ -48,20 +45,6 @@ STEPS, ROUNDS = 300, 5
 def step():
     out = model(harness.frame_batch(camera, True, dev, first, 1024))
     return out['rgb_fine'], out['depth_fine']
-
-
-def in_kernel_clock():
-    """GHz inside the last fine-pass launch (1024 workgroups of 256 samples in the 16-bit mode), median over workgroups."""
-    if not stamped:
-        return None
-    pairs = 512
-    buf = (ctypes.c_ulonglong * (2 * pairs))()
-    lib.snerf_debug_clock_stamps_forward_m16.restype = ctypes.c_int
-    lib.snerf_debug_clock_stamps_forward_m16.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]
-    torch.cuda.synchronize()
-    assert lib.snerf_debug_clock_stamps_forward_m16(buf, pairs) == 0
-    ratios = [buf[2 * i] / buf[2 * i + 1] * 0.1 for i in range(pairs) if buf[2 * i + 1] > 0]
-    return statistics.median(ratios) if ratios else None
 
 
 with torch.no_grad():
@@ -99,7 +82,7 @@ with torch.no_grad():
             launches, _ = ops.profile_collect(ops.PROFILE_MLP_FORWARD)
             kernel_ms = sum(launches) / STEPS
             ops.profile_enable(0)
-        return ms, kernel_ms, in_kernel_clock()
+        return ms, kernel_ms
 
     results = {arm: [] for arm in ('events', 'plain', 'graph')}
     for _ in range(ROUNDS):
@@ -108,9 +91,7 @@ with torch.no_grad():
 summary = {'precision': precision, 'library': os.path.basename(_lib.LIB_PATH), 'steps_per_round': STEPS, 'rounds': ROUNDS,
            'device': torch.cuda.get_device_name(0)}
 for arm, rows in results.items():
-    clocks = [r[2] for r in rows if r[2] is not None]
     kernel = [r[1] for r in rows if r[1] is not None]
     summary[arm] = {'ms_per_step_median': statistics.median(r[0] for r in rows), 'ms_per_step_all': [round(r[0], 4) for r in rows],
-                    'mlp_kernel_ms_per_step': statistics.median(kernel) if kernel else None,
-                    'in_kernel_clock_ghz': statistics.median(clocks) if clocks else None}
+                    'mlp_kernel_ms_per_step': statistics.median(kernel) if kernel else None}
 print(json.dumps(summary))

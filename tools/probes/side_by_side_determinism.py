@@ -32,7 +32,7 @@ for i in range(repeats):
         if not torch.equal(g, ref[n]):
             d = float((g - ref[n]).abs().max()) / (float(ref[n].abs().max()) + 1e-30)
             bad.setdefault(n, []).append((i, d))
-            if os.environ.get('SNERF_PROBE_WHERE'):
+            if os.environ.get('SIDE_BY_SIDE_WHERE'):
                 w = (g != ref[n]).nonzero()
                 lo, hi = w.min(0).values.tolist(), w.max(0).values.tolist()
                 print('rep', i, n, tuple(g.shape), 'elements', int(w.shape[0]), 'box', lo, hi, 'rel %.1e' % d, flush=True)

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Soak of the side-by-side levels (csrc/render.hip): N training iterations at 512 rows per batch (32 768 coarse samples per
 sub-batch call: every level side by side), eager, on a given build of the library; prints the final loss, the PSNR of a training
-view and a SHA-256 of every parameter.  Run once on the shipped library and once on gpurun_abl_noside.so
-(tools/probes/build_variant.py noside --only render -DSNERF_PROBE_NO_SIDE_BY_SIDE): identical arithmetic in another stream
-arrangement must give the SAME hash -- a race between levels would not.
+view and a SHA-256 of every parameter.  Run once on each of two builds of the library (profiles/r05_soak_side_by_side.jsonl: the
+shipped one and a build whose levels ran in order): identical arithmetic in another stream arrangement must give the SAME
+hash -- a race between levels would not.
     usage: soak_side_by_side.py <lib.so> [iterations] [precision]"""
 import hashlib
 import json

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Soak of the side-by-side levels on the SIX-level model (augmentation MLPs at the fine level too: the case of DESIGN 10.6): N
 plain gradient-descent steps over 512-ray passes (every level side by side), each on another block of rays, on a given build of
-the library; prints a SHA-256 of every parameter.  The shipped library and gpurun_abl_noside.so (levels in order;
-tools/probes/build_variant.py noside --only render -DSNERF_PROBE_NO_SIDE_BY_SIDE) must end with the SAME hash.
+the library; prints a SHA-256 of every parameter.  Two builds of the same arithmetic (profiles/r05_soak_six_levels.jsonl: the
+shipped library and a build whose levels ran in order) must end with the SAME hash.
     usage: soak_six_levels.py <lib.so> [iterations] [precision]"""
 import hashlib
 import json

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Config 5's training iteration on a given build of the library (A/B of diagnostic variants, tools/probes/build_variant.py):
+"""Config 5's training iteration on a given build of the library (A/B of two builds):
 bench.py's own measurement (settle, warm-up, fenced timed steps) through the ctypes binding, which loads `_lib.LIB_PATH`
 (the TORCH_LIBRARY extension is linked against the shipped library).   usage: train_ab.py <lib.so> [precision] [steps]"""
 import json
