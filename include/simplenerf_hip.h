@@ -517,6 +517,28 @@ int snerf_lpips_tap_shape(int height, int width, int layer, int* tap_height, int
 int snerf_lpips_sums(const unsigned char* gt, const unsigned char* eval, const unsigned char* mask, int height, int width,
                      const float* packed, double* sums, float* const* taps, void* workspace, snerf_stream_t stream);
 
+/* The same five entry points with the backbone as an argument (ADDED within ABI version 10).  SNERF_LPIPS_ALEX behaves exactly as
+ * the functions above do; SNERF_LPIPS_VGG16 is lpips.LPIPS(net='vgg'), version 0.1, lin layers on, eval mode, spatial=False:
+ *
+ *   the same scaling layer; torchvision's vgg16 `features`: thirteen 3 x 3 stride-1 pad-1 convolutions with bias and ReLU (indices
+ *   0 2 | 5 7 | 10 12 14 | 17 19 21 | 24 26 28; channels 3->64 64->64 | 64->128 128->128 | 128->256 256->256 256->256 | 256->512
+ *   512->512 512->512 | 512->512 512->512 512->512), a 2 x 2 stride-2 maximum (no padding, floor mode) at each `|`; the five taps
+ *   are the ReLUs of convolutions 2, 7, 14, 21, 28 (64, 128, 256, 512, 512 channels); per tap and pixel the same v, LPIPS the
+ *   same sum of means.
+ *
+ * height, width >= 16 (16 -> 8 -> 4 -> 2 -> 1) and <= 16384.  Any other selector is SNERF_E_INVALID (a count or a size of 0).
+ * The arrays of snerf_lpips_net_pack hold 13 convolution weights ((c_out, c_in, 3, 3), in the order above) and biases and 5 lin
+ * weights for VGG-16; `layer` of snerf_lpips_net_tap_shape and the entries of `taps` and `sums` count the five taps.  A packed
+ * buffer belongs to the network it was packed for. */
+enum { SNERF_LPIPS_ALEX = 0, SNERF_LPIPS_VGG16 = 1 };
+long long snerf_lpips_net_packed_floats(int net);
+int snerf_lpips_net_pack(int net, const float* const* conv_weights, const float* const* conv_biases, const float* const* lin_weights,
+                         const float* scaling, float* packed, snerf_stream_t stream);
+long long snerf_lpips_net_workspace_bytes(int net, int height, int width);
+int snerf_lpips_net_tap_shape(int net, int height, int width, int layer, int* tap_height, int* tap_width, int* channels);
+int snerf_lpips_net_sums(int net, const unsigned char* gt, const unsigned char* eval, const unsigned char* mask, int height, int width,
+                         const float* packed, double* sums, float* const* taps, void* workspace, snerf_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Opt-in event timing of the dominant kernels (the measurement row, SURVEY 8d: "achieved" of the roofline is measured
  * live with HIP events on the stream the kernel is launched on).  While enabled, every snerf_mlp_forward[_train] launch

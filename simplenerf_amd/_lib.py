@@ -145,6 +145,12 @@ SIGNATURES = {
     'snerf_lpips_workspace_bytes': (c_longlong, [c_int, c_int]),
     'snerf_lpips_tap_shape': (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     'snerf_lpips_sums': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # the same with the backbone as the first argument (0 AlexNet, 1 VGG-16)
+    'snerf_lpips_net_packed_floats': (c_longlong, [c_int]),
+    'snerf_lpips_net_pack': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'snerf_lpips_net_workspace_bytes': (c_longlong, [c_int, c_int, c_int]),
+    'snerf_lpips_net_tap_shape': (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    'snerf_lpips_net_sums': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # include/simplenerf_train.h
     'snerf_loss_workspace_bytes': (c_longlong, []),
     'snerf_loss_forward': (c_int, [POINTER(LossTerm), c_int, c_int, c_longlong, _FP, _FP, c_void_p, c_void_p]),

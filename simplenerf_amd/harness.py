@@ -179,7 +179,8 @@ def evaluate_frames(model, configs: dict, frames, device, rank: int = 0, world_s
     frame may carry 'mask_views': {'depth_train' (T,h,w) float32, 'depth_test' (h,w) float32, 'extrinsics_train' (T,4,4),
     'extrinsic_test' (4,4), 'intrinsics_train' (T,3,3), 'intrinsic_test' (3,3) or None [, 'depth_error_threshold', 'min_views']} --
     the arguments of ``qa.visibility_mask``, which then computes the mask of the masked metrics on the device.
-    ``lpips_weights``: a ``qa.LpipsWeights``; every row then also carries LPIPS (and MaskedLPIPS where there is a mask).
+    ``lpips_weights``: a ``qa.LpipsWeights``; every row then also carries LPIPS (and MaskedLPIPS where there is a mask), on the
+    backbone the weights were packed for (AlexNet or VGG-16: one per call, under the same keys).
     Returns {'frames': [{'frame_num': ., metric: value rounded to 4 decimals, ...}], 'average': {metric: value}} with the
     reference's bookkeeping (``qa.summarise``) plus 'unrounded', the per-frame values before rounding.  With world_size > 1 each
     rank renders its block of every frame, rank 0 scores and the other ranks return None."""

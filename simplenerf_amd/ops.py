@@ -1191,29 +1191,48 @@ class IterationRing:
 LPIPS_MIN_EXTENT = 31      # the smallest side AlexNet's features accept: relu1 7 -> pool 3 -> pool 1
 # (c_out, c_in, kernel) of the five convolutions whose post-ReLU outputs are the taps
 LPIPS_CONVS = ((64, 3, 11), (192, 64, 5), (384, 192, 3), (256, 384, 3), (256, 256, 3))
+LPIPS_VGG_MIN_EXTENT = 16  # the smallest side VGG-16's features accept down to relu5_3: 16 -> 8 -> 4 -> 2 -> 1
+# (c_out, c_in, kernel) of VGG-16's thirteen convolutions, and which of them the five taps follow (relu1_2 .. relu5_3)
+LPIPS_VGG_CONVS = ((64, 3, 3), (64, 64, 3), (128, 64, 3), (128, 128, 3), (256, 128, 3), (256, 256, 3), (256, 256, 3), (512, 256, 3),
+                   (512, 512, 3), (512, 512, 3), (512, 512, 3), (512, 512, 3), (512, 512, 3))
+LPIPS_VGG_TAP_CONVS = (1, 3, 6, 9, 12)
+# net -> (the C ABI's selector, the name in messages, minimum extent, convolutions, the convolution each tap follows)
+_LPIPS_NETS = {'alex': (0, 'AlexNet', LPIPS_MIN_EXTENT, LPIPS_CONVS, (0, 1, 2, 3, 4)),
+               'vgg': (1, 'VGG-16', LPIPS_VGG_MIN_EXTENT, LPIPS_VGG_CONVS, LPIPS_VGG_TAP_CONVS)}
 
-_lpips_workspaces: Dict[torch.device, Tensor] = {}
+_lpips_workspaces: Dict[tuple, Tensor] = {}      # one per (device, network)
+
+
+def _lpips_net(net):
+    if net not in _LPIPS_NETS:
+        raise RuntimeError(f"net: expected 'alex' or 'vgg', got {net!r}")
+    return _LPIPS_NETS[net]
 
 
 def _pointer_array(tensors) -> ctypes.Array:
     return (ctypes.c_void_p * len(tensors))(*[0 if t is None else t.data_ptr() for t in tensors])
 
 
-def lpips_pack(conv_weights, conv_biases, lin_weights, shift=None, scale=None) -> Tensor:
-    """The 15 tensors of LPIPS-alex -> the packed fp32 device buffer ``lpips_sums`` reads (snerf_lpips_pack): every convolution
-    re-ordered to [k = (tap row, tap column, channel)][c_out].  ``conv_weights[l]`` float32 (c_out, c_in, k, k), ``conv_biases[l]``
-    (c_out), ``lin_weights[l]`` (c_out) (or (1, c_out, 1, 1)), all on one GPU; ``shift`` / ``scale``: three numbers each, the
-    scaling layer's buffers (default: the package's constants)."""
-    if not (len(conv_weights) == len(conv_biases) == len(lin_weights) == len(LPIPS_CONVS)):
-        raise RuntimeError(f'lpips_pack: expected {len(LPIPS_CONVS)} convolution weights, biases and lin weights')
+def lpips_pack(conv_weights, conv_biases, lin_weights, shift=None, scale=None, net: str = 'alex') -> Tensor:
+    """The tensors of LPIPS-alex (15) or LPIPS-vgg (13 + 13 + 5) -> the packed fp32 device buffer ``lpips_sums`` reads
+    (snerf_lpips_net_pack): every convolution re-ordered to [k = (tap row, tap column, channel)][c_out].  ``conv_weights[l]``
+    float32 (c_out, c_in, k, k), ``conv_biases[l]`` (c_out), ``lin_weights[t]`` (c_out of tap t) (or (1, c_out, 1, 1)), all on one
+    GPU; ``shift`` / ``scale``: three numbers each, the scaling layer's buffers (default: the package's constants)."""
+    selector, _, _, convs, tap_convs = _lpips_net(net)
+    if not (len(conv_weights) == len(conv_biases) == len(convs) and len(lin_weights) == len(tap_convs)):
+        if net == 'alex':
+            raise RuntimeError(f'lpips_pack: expected {len(LPIPS_CONVS)} convolution weights, biases and lin weights')
+        raise RuntimeError(f'lpips_pack: expected {len(convs)} convolution weights and biases and {len(tap_convs)} lin weights')
     weights, biases, lins = [], [], []
-    for l, (c_out, c_in, k) in enumerate(LPIPS_CONVS):
+    for l, (c_out, c_in, k) in enumerate(convs):
         weights.append(_typed(conv_weights[l], f'conv_weights[{l}]', (torch.float32,), (c_out, c_in, k, k)))
         biases.append(_typed(conv_biases[l], f'conv_biases[{l}]', (torch.float32,), (c_out,)))
-        lin = _typed(lin_weights[l], f'lin_weights[{l}]', (torch.float32,))
-        if tuple(lin.shape) not in ((c_out,), (1, c_out, 1, 1)):
-            raise RuntimeError(f'lin_weights[{l}]: expected shape {(1, c_out, 1, 1)} or {(c_out,)}, got {tuple(lin.shape)}')
-        lins.append(lin)
+        if l in tap_convs:
+            t = tap_convs.index(l)
+            lin = _typed(lin_weights[t], f'lin_weights[{t}]', (torch.float32,))
+            if tuple(lin.shape) not in ((c_out,), (1, c_out, 1, 1)):
+                raise RuntimeError(f'lin_weights[{t}]: expected shape {(1, c_out, 1, 1)} or {(c_out,)}, got {tuple(lin.shape)}')
+            lins.append(lin)
     dev = weights[0].device
     for name, group in (('conv_weights', weights), ('conv_biases', biases), ('lin_weights', lins)):
         for l, t in enumerate(group):
@@ -1228,46 +1247,50 @@ def lpips_pack(conv_weights, conv_biases, lin_weights, shift=None, scale=None) -
             raise RuntimeError('lpips_pack: shift and scale hold three values each')
         scaling = (ctypes.c_float * 6)(*values)
     lib = _lib.load()
-    packed = torch.empty((int(lib.snerf_lpips_packed_floats()),), dtype=torch.float32, device=dev)
+    packed = torch.empty((int(lib.snerf_lpips_net_packed_floats(selector)),), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        st = lib.snerf_lpips_pack(_pointer_array(weights), _pointer_array(biases), _pointer_array(lins), scaling, _ptr(packed), _stream())
+        st = lib.snerf_lpips_net_pack(selector, _pointer_array(weights), _pointer_array(biases), _pointer_array(lins), scaling, _ptr(packed),
+                                      _stream())
     _lib.check(st, 'snerf_lpips_pack')
     return packed
 
 
-def lpips_tap_shapes(height: int, width: int):
+def lpips_tap_shapes(height: int, width: int, net: str = 'alex'):
     """[(tap_h, tap_w, channels)] of the five taps for a height x width frame."""
+    selector = _lpips_net(net)[0]
     lib = _lib.load()
     shapes = []
-    for l in range(len(LPIPS_CONVS)):
+    for l in range(5):
         th, tw, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        _lib.check(lib.snerf_lpips_tap_shape(int(height), int(width), l, ctypes.byref(th), ctypes.byref(tw), ctypes.byref(c)),
+        _lib.check(lib.snerf_lpips_net_tap_shape(selector, int(height), int(width), l, ctypes.byref(th), ctypes.byref(tw), ctypes.byref(c)),
                    'snerf_lpips_tap_shape')
         shapes.append((th.value, tw.value, c.value))
     return shapes
 
 
-def lpips_sums(gt: Tensor, image: Tensor, packed: Tensor, mask: Optional[Tensor] = None, return_taps: bool = False):
-    """-> float64 (5) on the device: per AlexNet tap the sum over its pixels of sum_c lin_c (n_gt - n_eval)^2 (LPIPS is the sum of
-    sums[l] / (tap_h_l tap_w_l)); with a mask, eval is where(mask, eval, gt).  ``packed``: what ``lpips_pack`` returned.
-    ``return_taps``: also the five post-ReLU activations, float32 (2, tap_h, tap_w, channels), gt first, channels last."""
+def lpips_sums(gt: Tensor, image: Tensor, packed: Tensor, mask: Optional[Tensor] = None, return_taps: bool = False, net: str = 'alex'):
+    """-> float64 (5) on the device: per tap of the network the sum over its pixels of sum_c lin_c (n_gt - n_eval)^2 (LPIPS is the
+    sum of sums[l] / (tap_h_l tap_w_l)); with a mask, eval is where(mask, eval, gt).  ``packed``: what ``lpips_pack`` returned for
+    the same ``net``.  ``return_taps``: also the five post-ReLU activations, float32 (2, tap_h, tap_w, channels), gt first,
+    channels last."""
+    selector, name, min_extent, _, _ = _lpips_net(net)
     gt, image, mask, h, w = _image_pair(gt, image, mask)
-    if min(h, w) < LPIPS_MIN_EXTENT:
-        raise RuntimeError(f'gt_image: AlexNet needs {LPIPS_MIN_EXTENT} pixels on every side, the image extent is {h} x {w}')
+    if min(h, w) < min_extent:
+        raise RuntimeError(f'gt_image: {name} needs {min_extent} pixels on every side, the image extent is {h} x {w}')
     lib = _lib.load()
-    packed = _typed(packed, 'packed', (torch.float32,), (int(lib.snerf_lpips_packed_floats()),))
+    packed = _typed(packed, 'packed', (torch.float32,), (int(lib.snerf_lpips_net_packed_floats(selector)),))
     if packed.device != gt.device:
         raise RuntimeError(f'packed: expected a tensor on {gt.device}, got one on {packed.device}')
-    need = int(lib.snerf_lpips_workspace_bytes(h, w))
+    need = int(lib.snerf_lpips_net_workspace_bytes(selector, h, w))
     if need <= 0:
         raise RuntimeError(f'gt_image: the image extent {h} x {w} exceeds what the LPIPS kernels index')
     sums = torch.empty((5,), dtype=torch.float64, device=gt.device)
-    taps = [torch.empty((2, th, tw, c), dtype=torch.float32, device=gt.device) for th, tw, c in lpips_tap_shapes(h, w)] if return_taps else None
+    taps = [torch.empty((2, th, tw, c), dtype=torch.float32, device=gt.device) for th, tw, c in lpips_tap_shapes(h, w, net)] if return_taps else None
     with torch.cuda.device(gt.device):
-        ws = _lpips_workspaces.get(gt.device)
+        ws = _lpips_workspaces.get((gt.device, net))
         if ws is None or ws.numel() < need:
-            ws = _lpips_workspaces[gt.device] = torch.empty((need,), dtype=torch.uint8, device=gt.device)
-        st = lib.snerf_lpips_sums(_ptr(gt), _ptr(image), _ptr(mask), h, w, _ptr(packed), _ptr(sums),
-                                  None if taps is None else _pointer_array(taps), _ptr(ws), _stream())
+            ws = _lpips_workspaces[(gt.device, net)] = torch.empty((need,), dtype=torch.uint8, device=gt.device)
+        st = lib.snerf_lpips_net_sums(selector, _ptr(gt), _ptr(image), _ptr(mask), h, w, _ptr(packed), _ptr(sums),
+                                      None if taps is None else _pointer_array(taps), _ptr(ws), _stream())
     _lib.check(st, 'snerf_lpips_sums')
     return (sums, taps) if return_taps else sums

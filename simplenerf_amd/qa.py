@@ -16,7 +16,9 @@ LPIPS (04, 14) is ``lpips.LPIPS(net='alex')`` on the device (csrc/lpips.hip: the
 the fp32 matrix cores, fixed-order fp64 layer sums).  The build carries no network weights: ``LpipsWeights`` takes them from the
 caller's checkpoint files (torchvision's AlexNet + the package's ``alex.pth``, or a saved ``lpips.LPIPS`` state dict), read with
 ``torch.load(weights_only=True)`` -- neither package has to be installed.  The metric is pinned to tests/lpips_reference.py, a
-restatement of the package's published definition.
+restatement of the package's published definition.  ``net='vgg'`` is the same metric on VGG-16's thirteen convolutions (what much
+of the literature tabulates), through the same kernels and pinned to tests/lpips_vgg_reference.py; one ``LpipsWeights`` holds one
+backbone.
 
 The masks of the masked metrics are the stage's own first step (``src/qa/00_Common/src/mask_generators``): ``visibility_mask``
 splats the training views' depths into the test view and tests them against its depth, on the device (csrc/visibility_mask.hip).
@@ -194,23 +196,38 @@ def visibility_mask(depth_train: Tensor, depth_test: Tensor, extrinsics_train, e
 LPIPS_SHIFT, LPIPS_SCALE = (-.030, -.088, -.188), (.458, .448, .450)      # the package's ScalingLayer buffers
 _LPIPS_CONV_KEYS = {'lpips': ('net.slice1.0', 'net.slice2.3', 'net.slice3.6', 'net.slice4.8', 'net.slice5.10'),
                     'torchvision': ('features.0', 'features.3', 'features.6', 'features.8', 'features.10')}
+# VGG-16: torchvision's `features` indices of the thirteen convolutions; the package's slices keep those indices
+_VGG_FEATURES = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)
+_VGG_SLICES = (1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5)
+_LPIPS_VGG_CONV_KEYS = {'lpips': tuple(f'net.slice{s}.{i}' for s, i in zip(_VGG_SLICES, _VGG_FEATURES)),
+                        'torchvision': tuple(f'features.{i}' for i in _VGG_FEATURES)}
 
 
-def lpips_tensors(state_dict, lin_state_dict=None) -> Dict[str, object]:
-    """The 15 tensors of LPIPS-alex and the scaling layer's buffers out of checkpoint dictionaries, identified by name:
-    {'conv_weights': [5], 'conv_biases': [5], 'lin_weights': [5] as (c_out,), 'shift': (3,), 'scale': (3,)}, float32 on the host.
+def lpips_tensors(state_dict, lin_state_dict=None, net: str = 'alex') -> Dict[str, object]:
+    """The tensors of LPIPS-alex (5 + 5 + 5) or LPIPS-vgg (13 + 13 + 5) and the scaling layer's buffers out of checkpoint
+    dictionaries, identified by name: {'conv_weights': [5 | 13], 'conv_biases': [5 | 13], 'lin_weights': [5] as (c_out,),
+    'shift': (3,), 'scale': (3,)}, float32 on the host.  ``net`` chooses the network; it is never guessed from the file.
 
     ``state_dict``: a saved ``lpips.LPIPS(net='alex').state_dict()`` (``net.slice{1..5}.{0,3,6,8,10}.*``, ``lin{k}.model.1.weight``,
     ``scaling_layer.*``) or torchvision's AlexNet (``features.{0,3,6,8,10}.*``; classifier keys are ignored).  ``lin_state_dict``: the
     package's ``alex.pth`` (``lin{k}.model.1.weight`` only), needed with torchvision's file and overriding otherwise.  A missing or
-    mis-shaped tensor raises with its key; ``scaling_layer.shift`` / ``.scale``, where present, replace the package's constants."""
+    mis-shaped tensor raises with its key; ``scaling_layer.shift`` / ``.scale``, where present, replace the package's constants.
+
+    ``net='vgg'``: a saved ``lpips.LPIPS(net='vgg').state_dict()`` -- its convolutions are ``net.slice1.{0,2}``, ``net.slice2.{5,7}``,
+    ``net.slice3.{10,12,14}``, ``net.slice4.{17,19,21}``, ``net.slice5.{24,26,28}`` (the slices keep torchvision's indices), plus
+    ``lin{0..4}.model.1.weight`` and ``scaling_layer.*`` -- or torchvision's ``vgg16`` (``features.N.weight`` / ``.bias`` for N in
+    0 2 5 7 10 12 14 17 19 21 24 26 28; ``classifier.*`` is ignored) with the package's ``vgg.pth`` as ``lin_state_dict``.  This
+    key layout is written from the packages' published definitions; neither package was at hand to load a real file.  A file
+    of the other network fails on its first tensor, by name or by shape."""
+    convs, tap_convs = ops._lpips_net(net)[3:5]
     for name, value in (('state_dict', state_dict), ('lin_state_dict', lin_state_dict)):
         if not (value is None and name == 'lin_state_dict') and not hasattr(value, 'keys'):
             raise RuntimeError(f'{name}: expected a dictionary of tensors (a state dict), got {type(value).__name__}')
-    layout = next((name for name, keys in _LPIPS_CONV_KEYS.items() if any(k.startswith(keys[0] + '.') for k in state_dict.keys())), None)
+    conv_keys = _LPIPS_CONV_KEYS if net == 'alex' else _LPIPS_VGG_CONV_KEYS
+    layout = next((name for name, keys in conv_keys.items() if any(k.startswith(keys[0] + '.') for k in state_dict.keys())), None)
     if layout is None:
-        raise RuntimeError("state_dict: neither a saved lpips.LPIPS(net='alex') state dict (no key 'net.slice1.0.weight') nor "
-                           "torchvision's AlexNet (no key 'features.0.weight')")
+        raise RuntimeError(f"state_dict: neither a saved lpips.LPIPS(net='{net}') state dict (no key 'net.slice1.0.weight') nor "
+                           f"torchvision's {'AlexNet' if net == 'alex' else 'vgg16'} (no key 'features.0.weight')")
 
     def take(source, key, shape):
         if key not in source:
@@ -222,14 +239,17 @@ def lpips_tensors(state_dict, lin_state_dict=None) -> Dict[str, object]:
         return value.detach().to('cpu', torch.float32).contiguous()
 
     out: Dict[str, object] = {'conv_weights': [], 'conv_biases': [], 'lin_weights': []}
-    for l, (c_out, c_in, k) in enumerate(ops.LPIPS_CONVS):
-        prefix = _LPIPS_CONV_KEYS[layout][l]
+    for l, (c_out, c_in, k) in enumerate(convs):
+        prefix = conv_keys[layout][l]
         out['conv_weights'].append(take(state_dict, prefix + '.weight', (c_out, c_in, k, k)))
         out['conv_biases'].append(take(state_dict, prefix + '.bias', (c_out,)))
-        lin_key = f'lin{l}.model.1.weight'
+        if l not in tap_convs:
+            continue
+        t = tap_convs.index(l)
+        lin_key = f'lin{t}.model.1.weight'
         lin_source = lin_state_dict if lin_state_dict is not None else state_dict
-        if lin_key not in lin_source and f'lins.{l}.model.1.weight' in lin_source:
-            lin_key = f'lins.{l}.model.1.weight'
+        if lin_key not in lin_source and f'lins.{t}.model.1.weight' in lin_source:
+            lin_key = f'lins.{t}.model.1.weight'
         out['lin_weights'].append(take(lin_source, lin_key, (1, c_out, 1, 1)).reshape(c_out))
     for name, default in (('shift', LPIPS_SHIFT), ('scale', LPIPS_SCALE)):
         key = f'scaling_layer.{name}'
@@ -245,43 +265,51 @@ def lpips_tensors(state_dict, lin_state_dict=None) -> Dict[str, object]:
 
 
 class LpipsWeights:
-    """The weights of LPIPS-alex, packed once for the device kernels (``ops.lpips_pack``); pass it to ``lpips_metrics`` /
-    ``harness.evaluate_frames(lpips_weights=...)``.  ``tensors``: what ``lpips_tensors`` returned."""
+    """The weights of LPIPS-alex or LPIPS-vgg, packed once for the device kernels (``ops.lpips_pack``); pass it to ``lpips_metrics``
+    / ``harness.evaluate_frames(lpips_weights=...)``.  ``tensors``: what ``lpips_tensors`` returned for the same ``net``, which
+    ``.net`` keeps."""
 
-    def __init__(self, tensors: Dict[str, object], device='cuda'):
+    def __init__(self, tensors: Dict[str, object], device='cuda', net: str = 'alex'):
+        ops._lpips_net(net)
+        self.net = net
         self.device = torch.device(device)
         if self.device.type == 'cuda' and self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
         move = lambda group: [t.to(self.device) for t in group]
         self.packed = ops.lpips_pack(move(tensors['conv_weights']), move(tensors['conv_biases']), move(tensors['lin_weights']),
-                                     tensors['shift'], tensors['scale'])
+                                     tensors['shift'], tensors['scale'], net=net)
 
     @classmethod
-    def from_state_dict(cls, state_dict, lin_state_dict=None, device='cuda') -> 'LpipsWeights':
-        return cls(lpips_tensors(state_dict, lin_state_dict), device)
+    def from_state_dict(cls, state_dict, lin_state_dict=None, device='cuda', net: str = 'alex') -> 'LpipsWeights':
+        return cls(lpips_tensors(state_dict, lin_state_dict, net), device, net)
 
     @classmethod
-    def load(cls, path, lin_path=None, device='cuda') -> 'LpipsWeights':
+    def load(cls, path, lin_path=None, device='cuda', net: str = 'alex') -> 'LpipsWeights':
         """``path``: torchvision's AlexNet checkpoint (then ``lin_path`` is the package's ``alex.pth``) or a saved
-        ``lpips.LPIPS(net='alex').state_dict()``; plain ``torch.save``d dictionaries of tensors, read with ``weights_only=True``."""
+        ``lpips.LPIPS(net='alex').state_dict()``; with ``net='vgg'`` torchvision's ``vgg16-397923af.pth`` (then ``lin_path`` is the
+        package's ``vgg.pth``) or a saved ``lpips.LPIPS(net='vgg').state_dict()``.  Plain ``torch.save``d dictionaries of tensors,
+        read with ``weights_only=True``."""
         state = torch.load(path, map_location='cpu', weights_only=True)
         lin_state = None if lin_path is None else torch.load(lin_path, map_location='cpu', weights_only=True)
-        return cls.from_state_dict(state, lin_state, device)
+        return cls.from_state_dict(state, lin_state, device, net)
 
 
 def lpips_metrics(eval_image: Tensor, gt_image: Tensor, weights: LpipsWeights, mask: Optional[Tensor] = None) -> Dict[str, float]:
-    """LPIPS (AlexNet, version 0.1) of a uint8 (h,w,3) frame against its ground truth, both on the GPU; with a bool (h,w) ``mask``
-    also MaskedLPIPS, the score of (gt, where(mask, eval, gt)) -- exactly 0 for an all-false mask, as in the reference."""
+    """LPIPS (version 0.1, on the backbone of ``weights.net``: AlexNet or VGG-16) of a uint8 (h,w,3) frame against its ground truth,
+    both on the GPU; with a bool (h,w) ``mask`` also MaskedLPIPS, the score of (gt, where(mask, eval, gt)) -- exactly 0 for an
+    all-false mask, as in the reference."""
     gt, image, mask, h, w = ops._image_pair(gt_image, eval_image, mask)
-    if min(h, w) < ops.LPIPS_MIN_EXTENT:
-        raise RuntimeError(f'gt_image: AlexNet needs {ops.LPIPS_MIN_EXTENT} pixels on every side, the image extent is {h} x {w}')
+    net = weights.net if isinstance(weights, LpipsWeights) else 'alex'
+    _, name, min_extent = ops._lpips_net(net)[:3]
+    if min(h, w) < min_extent:
+        raise RuntimeError(f'gt_image: {name} needs {min_extent} pixels on every side, the image extent is {h} x {w}')
     if not isinstance(weights, LpipsWeights):
         raise RuntimeError(f'weights: expected qa.LpipsWeights, got {type(weights).__name__}')
-    sums = ops.lpips_sums(gt, image, weights.packed)
+    sums = ops.lpips_sums(gt, image, weights.packed, net=net)
     if mask is not None:
-        sums = torch.cat([sums, ops.lpips_sums(gt, image, weights.packed, mask)])
+        sums = torch.cat([sums, ops.lpips_sums(gt, image, weights.packed, mask, net=net)])
     sums = sums.cpu().numpy()                                   # 5 or 10 scalars cross to the host
-    pixels = [th * tw for th, tw, _ in ops.lpips_tap_shapes(h, w)]
+    pixels = [th * tw for th, tw, _ in ops.lpips_tap_shapes(h, w, net)]
     score = lambda layer_sums: float(sum(numpy.float64(s) / n for s, n in zip(layer_sums, pixels)))
     out = {'LPIPS': score(sums[:5])}
     if mask is not None:
