@@ -540,6 +540,48 @@ int snerf_lpips_net_sums(int net, const unsigned char* gt, const unsigned char* 
                          const float* packed, double* sums, float* const* taps, void* workspace, snerf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Q4  the sorts and the mask selection Q1 and Q2 consume: sorted depths for the median and the tie-averaged ranks
+ * (snerf_depth_error_sums, snerf_rank_correlation_sums), the stable sort of the splat keys between snerf_visibility_mask_project and
+ * _list_starts / _gather, and the selection of the masked pixels for the masked rank correlation.  Like Q1-Q3 these were ADDED
+ * within ABI version 10 (no existing struct or signature changed; a caller checks that the symbol exists).
+ *
+ * The sort is a least-significant-digit radix sort on 8-bit digits, ceil(key_bits / 8) passes of count, scan, scatter.  It is
+ * STABLE (equal keys keep their input order) and holds no atomic: the same input gives the same bits on every call.  The input is
+ * never written; the passes alternate between the output and the workspace so that the last one lands in the output.  The calls
+ * only enqueue on `stream`: no allocation, no synchronisation, no copy to the host.  count == 0 returns SNERF_OK at once (the
+ * compaction still writes a kept count of 0); count < 0 or >= 2^31, key_bits outside 1..32 and a NULL pointer are
+ * SNERF_E_INVALID before anything is enqueued.  Outputs must not overlap inputs.
+ *   workspace  device scratch of at least the query below (256-byte aligned, as hipMalloc returns it); no initial state, and calls
+ *              enqueued on ONE stream may share it
+ */
+/* bytes of scratch a sort of `count` keys of `key_bits` bits needs (key_bits = 32 for snerf_sort_f32); 0 for a count of 0 and for
+ * what the sorts refuse.  Never decreases as count grows. */
+long long snerf_sort_workspace_bytes(long long count, int key_bits);
+
+/* sorted  device (count) fp32, written: `values` ascending by the total order -inf < ... < -0 < +0 < ... < +inf < NaN.  -0 comes
+ *         before +0; every NaN, whatever its sign or payload, comes last and is returned as the quiet NaN 0x7FC00000.  On input
+ *         without NaN and -0 this is torch.sort(values).values / numpy.sort(values), bit for bit. */
+int snerf_sort_f32(const float* values, long long count, float* sorted, void* workspace, snerf_stream_t stream);
+
+/* keys         device (count) int32, 0 <= key < 2^key_bits (bits from key_bits up, rounded up to a multiple of 8, are not looked at)
+ * sorted_keys  device (count) int32, written: the keys ascending
+ * order        device (count) int64, written: the permutation of the stable sort, sorted_keys[j] = keys[order[j]], ascending within a
+ *              run of equal keys -- numpy.argsort(keys, kind='stable'); what snerf_visibility_mask_gather takes */
+int snerf_sort_keys_with_order(const int* keys, long long count, int key_bits, int* sorted_keys, long long* order, void* workspace,
+                               snerf_stream_t stream);
+
+/* bytes of scratch snerf_compact_f32_pair needs for `count` positions (0 for a count of 0 and for what it refuses) */
+long long snerf_compact_workspace_bytes(long long count);
+
+/* a_kept[j] = a[i_j], b_kept[j] = b[i_j] for the ascending positions i_j whose mask byte is not zero (count, scan, scatter: the
+ * output order is the input order).
+ *   a, b            device (count) fp32;  mask  device (count) bytes
+ *   a_kept, b_kept  device (count) fp32: the first kept[0] values are written, the rest is left alone
+ *   kept            device (1) int64, written: the number of kept positions */
+int snerf_compact_f32_pair(const float* a, const float* b, const unsigned char* mask, long long count, float* a_kept, float* b_kept,
+                           long long* kept, void* workspace, snerf_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Opt-in event timing of the dominant kernels (the measurement row, SURVEY 8d: "achieved" of the roofline is measured
  * live with HIP events on the stream the kernel is launched on).  While enabled, every snerf_mlp_forward[_train] launch
  * (kind SNERF_PROFILE_MLP_FORWARD) and every snerf_mlp_backward call (SNERF_PROFILE_MLP_BACKWARD) -- also those issued

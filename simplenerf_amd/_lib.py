@@ -151,6 +151,12 @@ SIGNATURES = {
     'snerf_lpips_net_workspace_bytes': (c_longlong, [c_int, c_int, c_int]),
     'snerf_lpips_net_tap_shape': (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     'snerf_lpips_net_sums': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # sorts and mask compaction (Q4)
+    'snerf_sort_workspace_bytes': (c_longlong, [c_longlong, c_int]),
+    'snerf_sort_f32': (c_int, [_FP, c_longlong, _FP, c_void_p, c_void_p]),
+    'snerf_sort_keys_with_order': (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'snerf_compact_workspace_bytes': (c_longlong, [c_longlong]),
+    'snerf_compact_f32_pair': (c_int, [_FP, _FP, c_void_p, c_longlong, _FP, _FP, c_void_p, c_void_p, c_void_p]),
     # include/simplenerf_train.h
     'snerf_loss_workspace_bytes': (c_longlong, []),
     'snerf_loss_forward': (c_int, [POINTER(LossTerm), c_int, c_int, c_longlong, _FP, _FP, c_void_p, c_void_p]),

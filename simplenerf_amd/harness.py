@@ -169,7 +169,7 @@ def predict_frame(model, configs: dict, camera: dict, device, rank: int = 0, wor
 
 @torch.no_grad()
 def evaluate_frames(model, configs: dict, frames, device, rank: int = 0, world_size: int = 1, ray_block: int = 65536,
-                    collective: Optional[bool] = None, lpips_weights=None) -> Optional[dict]:
+                    collective: Optional[bool] = None, lpips_weights=None, sorter: str = 'torch') -> Optional[dict]:
     """The reference's QA stage over a test set (src/qa/*), without the frames leaving the device: every frame is rendered
     through the path of ``predict_frame``, converted for display there (uint8 colour, depth clipped at 0) and scored against its
     targets by ``qa.image_metrics`` / ``qa.depth_metrics`` -- only the metrics' scalar sums cross to the host.
@@ -181,10 +181,12 @@ def evaluate_frames(model, configs: dict, frames, device, rank: int = 0, world_s
     the arguments of ``qa.visibility_mask``, which then computes the mask of the masked metrics on the device.
     ``lpips_weights``: a ``qa.LpipsWeights``; every row then also carries LPIPS (and MaskedLPIPS where there is a mask), on the
     backbone the weights were packed for (AlexNet or VGG-16: one per call, under the same keys).
+    ``sorter``: 'torch' or 'library', handed to ``qa.visibility_mask`` and ``qa.depth_metrics`` (who sorts and selects: same values).
     Returns {'frames': [{'frame_num': ., metric: value rounded to 4 decimals, ...}], 'average': {metric: value}} with the
     reference's bookkeeping (``qa.summarise``) plus 'unrounded', the per-frame values before rounding.  With world_size > 1 each
     rank renders its block of every frame, rank 0 scores and the other ranks return None."""
     from . import qa
+    qa._sorter(sorter)
     ndc = bool(configs['data_loader']['ndc'])
     suffix = '_fine' if 'fine_mlp' in configs['model'] else '_coarse'
     keys = [f'rgb{suffix}', f'depth{suffix}']
@@ -205,14 +207,14 @@ def evaluate_frames(model, configs: dict, frames, device, rank: int = 0, world_s
             views = frame['mask_views']
             mask = qa.visibility_mask(on_device(views['depth_train']), on_device(views['depth_test']), views['extrinsics_train'],
                                       views['extrinsic_test'], views['intrinsics_train'], views.get('intrinsic_test'),
-                                      float(views.get('depth_error_threshold', 0.05)), int(views.get('min_views', 2)))
+                                      float(views.get('depth_error_threshold', 0.05)), int(views.get('min_views', 2)), sorter=sorter)
         row = {'frame_num': frame['frame_num']}
         row.update(qa.image_metrics(image.reshape(h, w, 3), on_device(frame['image']), mask))
         if lpips_weights is not None:
             row.update(qa.lpips_metrics(image.reshape(h, w, 3), on_device(frame['image']), lpips_weights, mask))
         if frame.get('depth') is not None:
             row.update(qa.depth_metrics(depth.reshape(h, w), on_device(frame['depth']),
-                                        float(frame.get('depth_scale', 1.0)), float(frame.get('gt_depth_scale', 1.0)), mask))
+                                        float(frame.get('depth_scale', 1.0)), float(frame.get('gt_depth_scale', 1.0)), mask, sorter=sorter))
         rows.append(row)
     if rank != 0 and (world_size > 1 if collective is None else collective):
         return None

@@ -794,6 +794,85 @@ def visibility_mask_combine(mask_views: Tensor, min_views: int = 2) -> Tensor:
     return mask
 
 
+# ---------------------------------------------------------------------------------------------- Q4 sorts and mask compaction
+SORT_MAX_COUNT = 2 ** 31 - 1
+
+# scratch of the sorts and the compaction (second key / index buffers, digit counters), one per device, grown on demand; calls on
+# one device are ordered by the stream they are enqueued on
+_sort_workspaces: Dict[torch.device, Tensor] = {}
+
+
+def _sort_workspace(dev: torch.device, need: int) -> Tensor:
+    ws = _sort_workspaces.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = _sort_workspaces[dev] = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _flat(t: Tensor, name: str) -> int:
+    if t.dim() != 1:
+        raise RuntimeError(f'{name}: expected a flat tensor, got shape {tuple(t.shape)}')
+    if t.numel() > SORT_MAX_COUNT:
+        raise RuntimeError(f'{name}: {t.numel()} elements exceed the 2^31 - 1 the sort kernels index')
+    return t.numel()
+
+
+def sort_values(x: Tensor) -> Tensor:
+    """-> the flat float32 ``x`` sorted ascending (a stable radix sort in the HIP library): -0 before +0, every NaN last and returned
+    as the canonical quiet NaN; without NaN and -0 equal to ``torch.sort(x).values`` bit for bit.  ``x`` is not written."""
+    x = _typed(x, 'x', (torch.float32,))
+    n = _flat(x, 'x')
+    out = torch.empty_like(x)
+    if n == 0:
+        return out
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        ws = _sort_workspace(x.device, int(lib.snerf_sort_workspace_bytes(n, 32)))
+        st = lib.snerf_sort_f32(_ptr(x), n, _ptr(out), _ptr(ws), _stream())
+    _lib.check(st, 'snerf_sort_f32')
+    return out
+
+
+def sort_keys_with_order(keys: Tensor, key_bits: Optional[int] = None):
+    """-> (sorted_keys int32, order int64) of the flat non-negative int32 ``keys``: the STABLE ascending sort, order equal to
+    ``numpy.argsort(keys, kind='stable')`` -- what ``torch.sort(keys, stable=True)`` returns.  ``key_bits``: every key is below
+    2 ** key_bits (1..32; a caller that knows the bound of its keys saves passes, one per 8 bits); None = 32.  ``keys`` is not
+    written."""
+    keys = _typed(keys, 'keys', (torch.int32,))
+    n = _flat(keys, 'keys')
+    key_bits = 32 if key_bits is None else key_bits
+    if isinstance(key_bits, bool) or int(key_bits) != key_bits or not 1 <= int(key_bits) <= 32:
+        raise RuntimeError(f'key_bits: expected 1..32, got {key_bits}')
+    sorted_keys = torch.empty_like(keys)
+    order = torch.empty((n,), dtype=torch.int64, device=keys.device)
+    if n == 0:
+        return sorted_keys, order
+    lib = _lib.load()
+    with torch.cuda.device(keys.device):
+        ws = _sort_workspace(keys.device, int(lib.snerf_sort_workspace_bytes(n, int(key_bits))))
+        st = lib.snerf_sort_keys_with_order(_ptr(keys), n, int(key_bits), _ptr(sorted_keys), _ptr(order), _ptr(ws), _stream())
+    _lib.check(st, 'snerf_sort_keys_with_order')
+    return sorted_keys, order
+
+
+def compact_pair(a: Tensor, b: Tensor, mask: Tensor):
+    """-> (a[mask != 0], b[mask != 0]) of the flat float32 ``a``, ``b`` under the flat bool / uint8 ``mask``, in input order (count,
+    scan, scatter in the HIP library).  The kept count is read back from the device once, to size the results."""
+    a = _typed(a, 'a', (torch.float32,))
+    n = _flat(a, 'a')
+    b = _typed(b, 'b', (torch.float32,), (n,))
+    mask = _typed(mask, 'mask', (torch.bool, torch.uint8), (n,))
+    a_kept, b_kept = torch.empty_like(a), torch.empty_like(b)
+    kept = torch.empty((1,), dtype=torch.int64, device=a.device)
+    lib = _lib.load()
+    with torch.cuda.device(a.device):
+        ws = _sort_workspace(a.device, int(lib.snerf_compact_workspace_bytes(n)))
+        st = lib.snerf_compact_f32_pair(_ptr(a), _ptr(b), _ptr(mask), n, _ptr(a_kept), _ptr(b_kept), _ptr(kept), _ptr(ws), _stream())
+    _lib.check(st, 'snerf_compact_f32_pair')
+    count = int(kept.item())
+    return a_kept[:count], b_kept[:count]
+
+
 # ---------------------------------------------------------------------------------------------- f1 losses
 class LossTermSpec:
     """One masked mean-squared-error term of the fused loss evaluation (struct snerf_loss_term).  ``two_sided``: the

@@ -5,7 +5,8 @@ The reference scores the frames its Tester wrote with one script per metric (``c
 skimage, pandas and scipy on the host.  Here the frame never leaves the GPU: the HIP library reduces the uint8 image pair /
 the fp32 depth pair to a handful of sums (exact int64 for the image errors, fp64 for everything else, fixed-order reductions --
 csrc/metrics.hip) and the functions below evaluate the reference's expressions on those sums.  Sorting (for the median and the
-ranks) and mask compaction are torch calls on the device.
+ranks) and mask compaction are torch calls on the device, or -- ``sorter='library'`` -- the HIP library's own stable radix sort and
+order-preserving compaction (csrc/sort.hip).
 
 SSIM is pinned to a restatement of skimage's ``structural_similarity(gt, eval, multichannel=True, gaussian_weights=True,
 sigma=1.5, use_sample_covariance=False)`` on ``scipy.ndimage.gaussian_filter`` (tests/qa_reference.py), not to skimage itself.
@@ -36,6 +37,14 @@ Tensor = torch.Tensor
 IMAGE_METRICS = ('RMSE', 'PSNR', 'SSIM')
 DEPTH_METRICS = ('DepthRMSE', 'DepthMAE', 'DepthSROCC')
 SSIM_CROP = (ops.SSIM_WINDOW - 1) // 2     # skimage crops the map by (win_size - 1) // 2 before taking the mean
+SORTERS = ('torch', 'library')
+
+
+def _sorter(sorter) -> bool:
+    """True for the library's sort and compaction, False for torch's; anything else is refused."""
+    if sorter not in SORTERS:
+        raise RuntimeError(f"sorter: expected 'torch' or 'library', got {sorter!r}")
+    return sorter == 'library'
 
 
 def _ratio(numerator, denominator):
@@ -76,10 +85,12 @@ def ssim_map(eval_image: Tensor, gt_image: Tensor, mask: Optional[Tensor] = None
     return ops.ssim_sums(gt_image, eval_image, mask, return_map=True)[1]
 
 
-def _srocc(x: Tensor, y: Tensor) -> Optional[Tensor]:
+def _srocc(x: Tensor, y: Tensor, library: bool = False) -> Optional[Tensor]:
     """Rank-correlation sums of two flat fp32 device tensors (None when they are empty)."""
     if x.numel() == 0:
         return None
+    if library:
+        return ops.rank_correlation_sums(x, y, ops.sort_values(x), ops.sort_values(y))
     return ops.rank_correlation_sums(x, y, torch.sort(x).values, torch.sort(y).values)
 
 
@@ -93,10 +104,13 @@ def _correlation(sums) -> float:
 
 
 def depth_metrics(eval_depth: Tensor, gt_depth: Tensor, eval_scale: float = 1.0, gt_scale: float = 1.0,
-                  mask: Optional[Tensor] = None) -> Dict[str, float]:
+                  mask: Optional[Tensor] = None, sorter: str = 'torch') -> Dict[str, float]:
     """DepthRMSE, DepthMAE (normalised by the median of the scaled ground truth) and DepthSROCC of an fp32 (h,w) depth map, both
     on the GPU; with a bool (h,w) ``mask`` also the Masked* forms (an all-false mask gives nan).  ``eval_scale`` / ``gt_scale``:
-    the reference's per-side factors (get_depth_scale), applied before anything else."""
+    the reference's per-side factors (get_depth_scale), applied before anything else.  ``sorter``: 'torch' sorts and selects the
+    masked pixels with torch ops, 'library' with the HIP library's (``ops.sort_values``, ``ops.compact_pair``); the metrics are the
+    same values either way."""
+    library = _sorter(sorter)
     gt = ops._typed(gt_depth, 'gt_depth', (torch.float32,))
     if gt.dim() != 2 or gt.numel() < 1:
         raise RuntimeError(f'gt_depth: expected a non-empty shape (h, w), got {tuple(gt.shape)}')
@@ -104,14 +118,18 @@ def depth_metrics(eval_depth: Tensor, gt_depth: Tensor, eval_scale: float = 1.0,
     if mask is not None:
         mask = ops._typed(mask, 'mask', (torch.bool, torch.uint8), tuple(gt.shape))
     gt_flat, eval_flat = gt.reshape(-1), depth.reshape(-1)
-    sorted_gt = torch.sort(gt_flat).values
+    sort = ops.sort_values if library else (lambda values: torch.sort(values).values)
+    sorted_gt = sort(gt_flat)
     pieces = [ops.depth_error_sums(gt, depth, gt_scale, eval_scale, None, sorted_gt),
-              ops.rank_correlation_sums(gt_flat, eval_flat, sorted_gt, torch.sort(eval_flat).values)]
+              ops.rank_correlation_sums(gt_flat, eval_flat, sorted_gt, sort(eval_flat))]
     masked_ranks = None
     if mask is not None:
-        keep = mask.reshape(-1).bool()
         pieces.append(ops.depth_error_sums(gt, depth, gt_scale, eval_scale, mask))
-        masked_ranks = _srocc(gt_flat[keep], eval_flat[keep])
+        if library:
+            masked_ranks = _srocc(*ops.compact_pair(gt_flat, eval_flat, mask.reshape(-1)), library=True)
+        else:
+            keep = mask.reshape(-1).bool()
+            masked_ranks = _srocc(gt_flat[keep], eval_flat[keep])
         if masked_ranks is not None:
             pieces.append(masked_ranks)
     sums = torch.cat(pieces).cpu().numpy()                      # at most 14 scalars cross to the host
@@ -158,7 +176,7 @@ def visibility_cameras(extrinsics_train, extrinsic_test, intrinsics_train, intri
 
 
 def visibility_mask(depth_train: Tensor, depth_test: Tensor, extrinsics_train, extrinsic_test, intrinsics_train, intrinsic_test=None,
-                    depth_error_threshold: float = 0.05, min_views: int = 2, return_views: bool = False):
+                    depth_error_threshold: float = 0.05, min_views: int = 2, return_views: bool = False, sorter: str = 'torch'):
     """The mask of the reference's masked metrics, computed on the device: a test pixel is visible from a training view when that
     view's depth, splatted into the test view (``Warper.forward_warp``: bilinear proximity x depth weight 1 / exp(50 L / max L)),
     lands on it and agrees with ``depth_test`` to ``depth_error_threshold`` x the view's largest depth (``MaskComputer.compute_mask``);
@@ -170,7 +188,10 @@ def visibility_mask(depth_train: Tensor, depth_test: Tensor, extrinsics_train, e
     share one resolution.  Returns the bool (h,w) mask on the device; ``return_views``: (mask, per-view masks bool (T,h,w), warped
     depths float64 (T,h,w), weight sums float64 (T,h,w)).  Arithmetic is fp64 and free of atomics: the same input gives the same bits.
     As in the reference a point behind the test camera still splats (with the largest depth weight) and no image is warped; a source
-    whose projection is not finite, and a view whose depths give max L = 0, add nothing (undefined in the reference)."""
+    whose projection is not finite, and a view whose depths give max L = 0, add nothing (undefined in the reference).
+    ``sorter``: the stable sort of the splat keys -- 'torch' (``torch.sort(stable=True)``) or 'library' (``ops.sort_keys_with_order``
+    over just the bits the keys of this frame use); the stable order is unique, so the outputs are the same bits either way."""
+    library = _sorter(sorter)
     depth_train = ops._typed(depth_train, 'depth_train', (torch.float32,))
     if depth_train.dim() != 3 or depth_train.numel() < 1:
         raise RuntimeError(f'depth_train: expected a non-empty shape (views, h, w), got {tuple(depth_train.shape)}')
@@ -183,7 +204,11 @@ def visibility_mask(depth_train: Tensor, depth_test: Tensor, extrinsics_train, e
     cameras = visibility_cameras(_matrices(extrinsics_train, 'extrinsics_train', (views, 4, 4)), extrinsic_test,
                                  _matrices(intrinsics_train, 'intrinsics_train', (views, 3, 3)), intrinsic_test)
     points, keys, stats = ops.visibility_mask_project(depth_train, torch.from_numpy(cameras).to(depth_train.device))
-    sorted_keys, order = torch.sort(keys.reshape(-1), stable=True)     # every list in ascending source order
+    if library:     # (every key is below views * keys per view: project's layout, ops._visibility_extent)
+        key_bits = max(1, (views * ops._visibility_extent(views, h, w, 'depth_train') - 1).bit_length())
+        sorted_keys, order = ops.sort_keys_with_order(keys.reshape(-1), key_bits)
+    else:
+        sorted_keys, order = torch.sort(keys.reshape(-1), stable=True)     # every list in ascending source order
     starts = ops.visibility_mask_list_starts(sorted_keys, views, h, w)
     gathered = ops.visibility_mask_gather(points, order, starts, stats, depth_test, depth_error_threshold, return_views)
     mask_views = gathered[0] if return_views else gathered

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Time the scoring of ONE 756 x 1008 frame (image + depth, with a mask) on the device and with the host restatement the tests
 use (tests/qa_reference.py: numpy + scipy) on the same box.  A record, not a gate.
-    python tools/measure_qa.py [repeats]      -> one JSON line
+    python tools/measure_qa.py [repeats] [--sorter torch|library]      -> one JSON line
 device_ms: HIP events around everything ``qa.image_metrics`` + ``qa.depth_metrics`` enqueue (the error sums, SSIM plain and
-masked, two sorts, the mask compaction, the rank sums), warm, median of ``repeats`` (default 25); call_ms: a host clock around the
+masked, four sorts, the mask compaction, the rank sums -- sorts and compaction by torch or, with ``--sorter library``, by the HIP
+library), warm, median of ``repeats`` (default 25); call_ms: a host clock around the
 two calls, which end in the copy of their scalars to the host; host_ms: the restatement, median of 3."""
 import json
 import os
@@ -31,34 +32,39 @@ def frame(h=756, w=1008, seed=0):
     return gt, image, gt_depth, depth, rng.random((h, w)) < 0.7
 
 
-def enqueue(gt, image, gt_depth, depth, mask):
+def enqueue(gt, image, gt_depth, depth, mask, sorter='torch'):
     """What the two qa calls put on the stream, without their copy to the host."""
+    sort = ops.sort_values if sorter == 'library' else (lambda v: torch.sort(v).values)
     ops.image_error_sums(gt, image, mask)
     ops.ssim_sums(gt, image)
     ops.ssim_sums(gt, image, mask)
     g, e = gt_depth.reshape(-1), depth.reshape(-1)
-    sorted_gt = torch.sort(g).values
+    sorted_gt = sort(g)
     ops.depth_error_sums(gt_depth, depth, 1.0, 1.0, None, sorted_gt)
-    ops.rank_correlation_sums(g, e, sorted_gt, torch.sort(e).values)
+    ops.rank_correlation_sums(g, e, sorted_gt, sort(e))
     ops.depth_error_sums(gt_depth, depth, 1.0, 1.0, mask)
     keep = mask.reshape(-1)
-    gm, em = g[keep], e[keep]
-    ops.rank_correlation_sums(gm, em, torch.sort(gm).values, torch.sort(em).values)
+    gm, em = ops.compact_pair(g, e, keep) if sorter == 'library' else (g[keep], e[keep])
+    ops.rank_correlation_sums(gm, em, sort(gm), sort(em))
 
 
 def main():
-    repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 25
+    args = sys.argv[1:]
+    sorter = args.pop(args.index('--sorter') + 1) if '--sorter' in args else 'torch'
+    args = [a for a in args if a != '--sorter']
+    qa._sorter(sorter)
+    repeats = int(args[0]) if args else 25
     host = frame()
     on_device = [torch.as_tensor(a).to(DEV) for a in host]
     gt, image, gt_depth, depth, mask = on_device
     for _ in range(5):
-        enqueue(*on_device)
+        enqueue(*on_device, sorter)
     torch.cuda.synchronize()
     device_ms, call_ms = [], []
     for _ in range(repeats):
         start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         start.record()
-        enqueue(*on_device)
+        enqueue(*on_device, sorter)
         stop.record()
         stop.synchronize()
         device_ms.append(start.elapsed_time(stop))
@@ -66,7 +72,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         got = qa.image_metrics(image, gt, mask)
-        got.update(qa.depth_metrics(depth, gt_depth, mask=mask))
+        got.update(qa.depth_metrics(depth, gt_depth, mask=mask, sorter=sorter))
         call_ms.append(1e3 * (time.perf_counter() - t0))
     host_ms = []
     for _ in range(3):
@@ -76,7 +82,7 @@ def main():
         host_ms.append(1e3 * (time.perf_counter() - t0))
     qa_reference.assert_close(got, want)
     print(json.dumps({'what': 'score one 756x1008 frame: RMSE/PSNR/SSIM + depth RMSE/MAE/SROCC, plain and masked', 'repeats': repeats,
-                      'device_ms_median': statistics.median(device_ms), 'device_ms_min': min(device_ms), 'device_ms_max': max(device_ms),
+                      'sorter': sorter, 'device_ms_median': statistics.median(device_ms), 'device_ms_min': min(device_ms), 'device_ms_max': max(device_ms),
                       'call_ms_median': statistics.median(call_ms), 'host_restatement_ms_median': statistics.median(host_ms),
                       'host_threads': torch.get_num_threads(), 'PSNR': got['PSNR'], 'SSIM': got['SSIM']}))
 
