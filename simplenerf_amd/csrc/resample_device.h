@@ -83,6 +83,7 @@ __host__ __device__ inline int resample_scratch_floats(int s_c, int s_f) { retur
 // deterministic linspace; `out`: the ray's s_c + s_f merged depths (global); `scratch`: resample_scratch_floats of LDS owned
 // by this wave.  CDF: the reference's own summation orders (see below; until round 3 a 64-lane fp32 shuffle scan, which
 // moved 0.02-0.18 % of the samples on identical inputs).  Search: binary search of the LDS-resident CDF.  Merge: every element of [coarse | samples] is scattered to its rank.
+// The whole wave must call this (the merge votes across its lanes).
 __device__ __forceinline__ void resample_wave(const float* __restrict__ zc, const float* __restrict__ wc, int s_c, int s_f,
                                               const float* __restrict__ u, float* __restrict__ out, float* scratch, int lane) {
     const int total = s_c + s_f;
@@ -137,12 +138,30 @@ __device__ __forceinline__ void resample_wave(const float* __restrict__ zc, cons
     }
     snerf::wave_lds_sync();
 
-    // sort(cat(coarse, samples)) (:314) as a merge by rank: the coarse depths are ascending (linspace, or jittered
-    // inside disjoint strata), so the rank of a sample among them is a binary search; the samples are ascending too
-    // when u is the deterministic linspace (inverse CDF is monotone), otherwise their mutual order is counted.
-    // Ties: coarse before samples, equal samples by index -- a valid total order, and equal values are interchangeable.
+    // sort(cat(coarse, samples)) (:314) as a merge by rank: every element of [coarse | samples] is scattered to its rank under
+    // the total order (value, position in the concatenation) -- ties: coarse before samples, equal samples by index; equal
+    // values are interchangeable.  The coarse depths are ascending as a rule (linspace, or jittered inside disjoint strata), so
+    // the rank of a sample among them is a binary search; the samples are ascending too when u is the deterministic linspace
+    // (the inverse CDF is monotone), otherwise their mutual order is counted.
+    // Neither holds to the last bit: near * (1 - t) + far * t rounds three times, so over a range of a few ulps (far within
+    // ~2^-17 of near) the reference's own coarse depths step back and forth, and the bin mid-points and samples with them.
+    // Searched ranks would then put two elements on one slot and leave another unwritten, so the wave checks the orders it is
+    // about to rely on and, where one does not hold, counts every element's rank in the concatenation instead.
     const float* smp = merged + s_c;
     const bool sorted_samples = (u == nullptr);
+    int ascending = 1;
+    for (int j = lane; j + 1 < s_c; j += 64) ascending &= merged[j] <= merged[j + 1];
+    if (sorted_samples)
+        for (int k = lane; k + 1 < s_f; k += 64) ascending &= smp[k] <= smp[k + 1];
+    if (!__all(ascending)) {
+        for (int i = lane; i < total; i += 64) {
+            const float v = merged[i];
+            int rank = 0;
+            for (int q = 0; q < total; ++q) { const float x = merged[q]; rank += (x < v) || (x == v && q < i); }
+            out[rank] = v;
+        }
+        return;
+    }
     for (int j = lane; j < s_c; j += 64) {          // coarse j: j + #{samples < z_j}
         const float v = merged[j];
         int below;
