@@ -582,6 +582,67 @@ int snerf_compact_f32_pair(const float* a, const float* b, const unsigned char* 
                            long long* kept, void* workspace, snerf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Q5  the rest of the reference's Warper (src/qa/00_Common/src/mask_generators/Warper.py) on the device: forward_warp's colour frame
+ * and flow, bilinear_splatting of any (height, width, channels) frame along any flow, and bilinear_interpolation, the backward warp.
+ * Like Q1-Q4 these were ADDED within ABI version 10 (no existing struct or signature changed; a caller checks that the symbol
+ * exists).  ONE frame per call; channels is 1..4; a frame is interleaved (height, width, channels); masks are bytes, non-zero = true,
+ * and may be NULL (all true).  views = 1 in every Q2 / Q4 call of the recipes:
+ *
+ *   splat along a flow    snerf_warp_positions_from_flow -> snerf_sort_keys_with_order (or any STABLE sort of `keys`) ->
+ *                         snerf_visibility_mask_list_starts(views = 1) -> snerf_warp_splat_gather
+ *   forward_warp          snerf_warp_project -> the same sort and list starts, ONCE -> snerf_warp_splat_gather of the uint8 frame
+ *                         (is_image) and snerf_warp_splat_gather of the Z plane of `points` (points + height * width, SNERF_WARP_F64,
+ *                         1 channel): the warped depth, bit for bit what snerf_visibility_mask_gather returns for that view
+ *   backward warp         snerf_warp_interpolate alone
+ *
+ * Semantics are Q2's (padded grid, floor and ceil before the clip, weight prox / exp(50 L / max L), a point behind the camera splats
+ * with the largest weight).  A source whose mask1 or flow12_mask is false adds nothing (the reference multiplies its weight by 0),
+ * yet max L is the maximum over ALL pixels of the depth, as the reference's log_depth1.max() is.  All arithmetic is fp64 on inputs
+ * widened first and is compiled without FMA contraction: a position computed from a flow, (flow + grid) + 1, and every fp64 output
+ * of snerf_warp_interpolate equal numpy's bit for bit; the splat differs from numpy by the rounding of exp / log and of the order
+ * of its sums only.  No floating-point atomic: two calls on the same input return the same bits.  Not pinned by the reference
+ * (undefined there) and given no contribution: a source or a backward-warped pixel whose position is not finite or leaves int32, a
+ * source whose depth is not finite, a view whose max L is 0; with is_image a NaN value is stored as 0.  The calls only enqueue on
+ * `stream`: no allocation, no synchronisation.  (height + 1)(width + 1) + 1 must stay below 2^31.
+ */
+enum { SNERF_WARP_U8 = 0, SNERF_WARP_F32 = 1, SNERF_WARP_F64 = 2 };
+
+/* bytes of scratch snerf_warp_project / snerf_warp_positions_from_flow need (0 for an extent they refuse); no initial state */
+long long snerf_warp_workspace_bytes(int height, int width);
+
+/* The projection of snerf_visibility_mask_project for ONE view (the same kernel: points, keys and stats[0] are the bits that
+ * call returns for the view when mask1 is NULL), which also writes the flow.
+ *   depth1  device (height, width) fp32;  camera  device (30) fp64, one row of Q2's `cameras`;  mask1  device (height, width) or NULL
+ *   points  device (3, height, width) fp64, written;  keys  device (height, width) int32, written (0 .. (height+1)(width+1), the last
+ *           the discard list);  stats  device (2) fp64, written: max L, max depth1
+ *   flow12  device (height, width, 2) fp64, written: (q0 / q2 - x, q1 / q2 - y) */
+int snerf_warp_project(const float* depth1, const double* camera, const unsigned char* mask1, int height, int width, double* points,
+                       int* keys, double* stats, double* flow12, void* workspace, snerf_stream_t stream);
+
+/* X = (flow_x + x) + 1, Y = (flow_y + y) + 1, Z = depth1; outputs as above (stats[1] = max depth1).
+ *   flow12  device (height, width, 2) fp64;  depth1  device (height, width) of depth_type SNERF_WARP_F32 or SNERF_WARP_F64
+ *   mask1, flow12_mask  device (height, width) bytes or NULL */
+int snerf_warp_positions_from_flow(const double* flow12, const void* depth1, int depth_type, const unsigned char* mask1,
+                                   const unsigned char* flow12_mask, int height, int width, double* points, int* keys, double* stats,
+                                   void* workspace, snerf_stream_t stream);
+
+/* points, stats  as written above;  order  the int64 permutation of the STABLE sort of keys;  starts  snerf_visibility_mask_list_starts
+ * values  device (height, width, channels) of value_type: what every source carries
+ * warped  device (height, width, channels), written: sum v weight / sum weight where sum weight > 0, else 0 -- fp64, or with is_image
+ *         (SNERF_WARP_U8 values only) clipped to [0, 255], rounded half to even, uint8
+ * mask2   device (height, width) bytes, written: sum weight > 0 */
+int snerf_warp_splat_gather(const double* points, const long long* order, const int* starts, const double* stats, const void* values,
+                            int value_type, int channels, int is_image, int height, int width, void* warped, unsigned char* mask2,
+                            snerf_stream_t stream);
+
+/* Warper.bilinear_interpolation: warped[y, x] = nr / dr where dr > 0, else 0, over the four taps of the zero-padded frame2 / mask2 at
+ * the padded position ((flow_x + x) + 1, (flow_y + y) + 1), nr = sum prox flow12_mask frame2 mask2, dr = sum prox flow12_mask mask2,
+ * both added in the order nw, sw, ne, se.  warped as above (fp64, or uint8 with is_image); mask1 bytes, written: dr > 0. */
+int snerf_warp_interpolate(const void* frame2, int value_type, int channels, const unsigned char* mask2, const double* flow12,
+                           const unsigned char* flow12_mask, int is_image, int height, int width, void* warped, unsigned char* mask1,
+                           snerf_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Opt-in event timing of the dominant kernels (the measurement row, SURVEY 8d: "achieved" of the roofline is measured
  * live with HIP events on the stream the kernel is launched on).  While enabled, every snerf_mlp_forward[_train] launch
  * (kind SNERF_PROFILE_MLP_FORWARD) and every snerf_mlp_backward call (SNERF_PROFILE_MLP_BACKWARD) -- also those issued

@@ -157,6 +157,15 @@ SIGNATURES = {
     'snerf_sort_keys_with_order': (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'snerf_compact_workspace_bytes': (c_longlong, [c_longlong]),
     'snerf_compact_f32_pair': (c_int, [_FP, _FP, c_void_p, c_longlong, _FP, _FP, c_void_p, c_void_p, c_void_p]),
+    # the Warper: colour splat, flow, backward warp (Q5)
+    'snerf_warp_workspace_bytes': (c_longlong, [c_int, c_int]),
+    'snerf_warp_project': (c_int, [_FP, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'snerf_warp_positions_from_flow': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p]),
+    'snerf_warp_splat_gather': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                        c_void_p, c_void_p]),
+    'snerf_warp_interpolate': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                       c_void_p]),
     # include/simplenerf_train.h
     'snerf_loss_workspace_bytes': (c_longlong, []),
     'snerf_loss_forward': (c_int, [POINTER(LossTerm), c_int, c_int, c_longlong, _FP, _FP, c_void_p, c_void_p]),

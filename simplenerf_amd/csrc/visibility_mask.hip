@@ -13,102 +13,15 @@
 
 #include "snerf_common.h"
 #include "splat_cells.h"
+#include "splat_project.h"
 
 namespace {
 
 using namespace snerf::splat;
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kMaxPartials = 1024;   // workgroups per view of the projection
-constexpr int kCamera = 30;          // doubles per training view: inv(K_train) 3x3 | rows 0..2 of E_test inv(E_train) 3x4 | K_test 3x3
+constexpr int kBlock = kProjectBlock;
 
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-// Maximum of `v` over the workgroup, valid in thread 0 (fmax: a NaN is ignored).  `lds` holds kWaves values; reusable after the call.
-__device__ __forceinline__ double block_max(double v, double* lds) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double m = lds[0];
-#pragma unroll
-    for (int k = 1; k < kWaves; ++k) m = fmax(m, lds[k]);
-    return m;
-}
-
-// ------------------------------------------------------------------------------------------------ project
-// grid (blocks, views).  Per source pixel: Warper.compute_transformed_points in its own order (inv(K_train) (x, y, 1), times the
-// depth, the 4x4 transform, K_test), the position through the reference's flow round trip ((q / q2 - grid) + grid) + 1, its key.
-// partial = (max L, max d_train) of the workgroup's pixels.
-__global__ void __launch_bounds__(kBlock) project_kernel(const float* __restrict__ depth_train, const double* __restrict__ cameras, int height,
-                                                         int width, double* __restrict__ points, int* __restrict__ keys,
-                                                         double* __restrict__ partials) {
-    __shared__ double lds[kWaves];
-    const int view = blockIdx.y;
-    const long long n = (long long)height * width;
-    const double* cam = cameras + (long long)view * kCamera;
-    double ki[9], tr[12], k2[9];
-#pragma unroll
-    for (int j = 0; j < 9; ++j) ki[j] = cam[j];
-#pragma unroll
-    for (int j = 0; j < 12; ++j) tr[j] = cam[9 + j];
-#pragma unroll
-    for (int j = 0; j < 9; ++j) k2[j] = cam[21 + j];
-    const float* depth = depth_train + view * n;
-    double* px = points + (long long)view * 3 * n;
-    double* py = px + n;
-    double* pz = py + n;
-    const int key_base = view * keys_per_view(height, width);
-    double max_l = 0.0, max_d = -INFINITY;
-    const long long stride = (long long)gridDim.x * kBlock;
-    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-        const int yi = (int)(i / width), xi = (int)(i - (long long)yi * width);
-        const double x = (double)xi, y = (double)yi, d = (double)depth[i];
-        double p[3], t[3], q[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) p[j] = d * (ki[3 * j] * x + ki[3 * j + 1] * y + ki[3 * j + 2]);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) t[j] = tr[4 * j] * p[0] + tr[4 * j + 1] * p[1] + tr[4 * j + 2] * p[2] + tr[4 * j + 3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) q[j] = k2[3 * j] * t[0] + k2[3 * j + 1] * t[1] + k2[3 * j + 2] * t[2];
-        const double X = ((q[0] / q[2] - x) + x) + 1.0, Y = ((q[1] / q[2] - y) + y) + 1.0, Z = q[2];
-        px[i] = X;
-        py[i] = Y;
-        pz[i] = Z;
-        keys[view * n + i] = key_base + source_key(X, Y, Z, height, width);
-        max_l = fmax(max_l, log_depth(Z));
-        max_d = fmax(max_d, d);
-    }
-    max_l = block_max(max_l, lds);
-    max_d = block_max(max_d, lds);
-    if (threadIdx.x == 0) {
-        double* out = partials + ((long long)view * gridDim.x + blockIdx.x) * 2;
-        out[0] = max_l;
-        out[1] = max_d;
-    }
-}
-
-// grid (views), ONE workgroup per view: stats[view] = (max L, max d_train) over the view's partials, thread t taking b = t, t + kBlock, ...
-__global__ void __launch_bounds__(kBlock) fold_max_kernel(const double* __restrict__ partials, int num_partials, double* __restrict__ stats) {
-    __shared__ double lds[kWaves];
-    const double* in = partials + (long long)blockIdx.x * num_partials * 2;
-    double max_l = 0.0, max_d = -INFINITY;
-    for (int b = threadIdx.x; b < num_partials; b += kBlock) {
-        max_l = fmax(max_l, in[2 * b]);
-        max_d = fmax(max_d, in[2 * b + 1]);
-    }
-    max_l = block_max(max_l, lds);
-    max_d = block_max(max_d, lds);
-    if (threadIdx.x == 0) {
-        stats[2 * blockIdx.x] = max_l;
-        stats[2 * blockIdx.x + 1] = max_d;
-    }
-}
+// (project: project_kernel of splat_project.h, shared with the Warper; here without a source mask and without the flow)
 
 // ------------------------------------------------------------------------------------------------ list starts
 // starts[k] = first index with sorted_keys[i] >= k (lower bound), k = 0 .. num_keys: list k is sorted positions starts[k] .. starts[k + 1].
@@ -178,19 +91,6 @@ __global__ void __launch_bounds__(kBlock) combine_kernel(const unsigned char* __
     }
 }
 
-inline int project_blocks(long long pixels) {
-    long long blocks = (pixels + kBlock - 1) / kBlock;
-    if (blocks > kMaxPartials) blocks = kMaxPartials;
-    return blocks < 1 ? 1 : (int)blocks;
-}
-
-// views * height * width sources and views * keys_per_view keys must both fit int32 (keys, list starts)
-inline bool fits(int views, int height, int width) {
-    if (views < 1 || height < 1 || width < 1) return false;
-    const long long keys = (long long)views * ((long long)(height + 1) * (width + 1) + 1);
-    return keys < 2147483647LL && (long long)views <= 65535;
-}
-
 }  // namespace
 
 extern "C" long long snerf_visibility_mask_workspace_bytes(int views, int height, int width) {
@@ -204,8 +104,8 @@ extern "C" int snerf_visibility_mask_project(const float* depth_train, const dou
     SNERF_REQUIRE(fits(views, height, width), "visibility_mask_project: %d views of %d x %d are empty or exceed int32 keys", views, height, width);
     const int blocks = project_blocks((long long)height * width);
     double* partials = (double*)workspace;
-    hipLaunchKernelGGL(project_kernel, dim3(blocks, views), dim3(kBlock), 0, (hipStream_t)stream, depth_train, cameras, height, width,
-                       points, keys, partials);
+    hipLaunchKernelGGL(project_kernel, dim3(blocks, views), dim3(kBlock), 0, (hipStream_t)stream, depth_train, cameras,
+                       (const unsigned char*)nullptr, height, width, points, keys, (double*)nullptr, partials);
     hipLaunchKernelGGL(fold_max_kernel, dim3(views), dim3(kBlock), 0, (hipStream_t)stream, (const double*)partials, blocks, stats);
     return snerf::check_launch("visibility_mask_project");
 }

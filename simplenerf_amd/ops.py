@@ -873,6 +873,146 @@ def compact_pair(a: Tensor, b: Tensor, mask: Tensor):
     return a_kept[:count], b_kept[:count]
 
 
+# ---------------------------------------------------------------------------------------------- Q5 the Warper
+WARP_U8, WARP_F32, WARP_F64 = 0, 1, 2      # enum SNERF_WARP_*
+_WARP_TYPES = {torch.uint8: WARP_U8, torch.float32: WARP_F32, torch.float64: WARP_F64}
+WARP_MAX_CHANNELS = 4
+
+
+def _warp_frame(frame, name: str, is_image: bool, extent=None):
+    """A frame of the Warper: (h, w, c), c in 1..4, uint8 with ``is_image`` and float32 / float64 without.  -> (frame, h, w, c)."""
+    frame = _typed(frame, name, (torch.uint8, torch.float32, torch.float64))
+    if is_image and frame.dtype != torch.uint8:
+        raise RuntimeError(f'{name}: is_image expects a uint8 frame (the result is rounded to uint8), got {frame.dtype}')
+    if not is_image and frame.dtype == torch.uint8:
+        raise RuntimeError(f'{name}: expected float32 or float64 without is_image, got {frame.dtype}')
+    if frame.dim() != 3 or frame.numel() < 1:
+        raise RuntimeError(f'{name}: expected a non-empty shape (h, w, c), got {tuple(frame.shape)}')
+    h, w, c = (int(s) for s in frame.shape)
+    if not 1 <= c <= WARP_MAX_CHANNELS:
+        raise RuntimeError(f'{name}: expected 1..{WARP_MAX_CHANNELS} channels (h, w, c), got {c} in {tuple(frame.shape)}')
+    if extent is not None and (h, w) != tuple(extent):
+        raise RuntimeError(f'{name}: expected shape ({extent[0]}, {extent[1]}, c), got {tuple(frame.shape)}')
+    _visibility_extent(1, h, w, name)
+    return frame, h, w, c
+
+
+def _warp_mask(mask, name: str, h: int, w: int):
+    return None if mask is None else _typed(mask, name, (torch.bool, torch.uint8), (h, w))
+
+
+def _warp_together(dev: torch.device, **operands) -> None:
+    """Every operand of one call lives on the device the call is enqueued on: a pointer of another device is refused by name."""
+    for name, t in operands.items():
+        if t is not None and t.device != dev:
+            raise RuntimeError(f'{name}: expected a tensor on {dev}, the device of the call\'s first operand, got one on {t.device}')
+
+
+# the projection's scratch (per-workgroup maxima) is the masks' buffer, _visibility_workspaces: one per device, grown on demand;
+# every call writes it before it reads it, and calls on one device are ordered by the stream they are enqueued on
+def _warp_workspace(lib, dev: torch.device, h: int, w: int) -> Tensor:
+    need = int(lib.snerf_warp_workspace_bytes(h, w))
+    ws = _visibility_workspaces.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = _visibility_workspaces[dev] = torch.empty((need,), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def warp_project(depth1: Tensor, camera: Tensor, mask1: Optional[Tensor] = None):
+    """``visibility_mask_project`` for ONE (h,w) float32 depth (``camera``: float64 (30) on the device, one row of its table), which
+    also returns the flow and sends the sources ``mask1`` drops to the discard list.  -> points float64 (1,3,h,w), keys int32 (1,h,w),
+    stats float64 (1,2), flow12 float64 (h,w,2): what ``visibility_mask_list_starts`` / ``warp_splat_gather`` take with views = 1."""
+    depth1 = _typed(depth1, 'depth1', (torch.float32,))
+    if depth1.dim() != 2:
+        raise RuntimeError(f'depth1: expected shape (h, w), got {tuple(depth1.shape)}')
+    h, w = (int(s) for s in depth1.shape)
+    _visibility_extent(1, h, w, 'depth1')
+    camera = _typed(camera, 'camera', (torch.float64,), (VISIBILITY_CAMERA,))
+    mask1 = _warp_mask(mask1, 'mask1', h, w)
+    dev = depth1.device
+    _warp_together(dev, camera=camera, mask1=mask1)
+    points = torch.empty((1, 3, h, w), dtype=torch.float64, device=dev)
+    keys = torch.empty((1, h, w), dtype=torch.int32, device=dev)
+    stats = torch.empty((1, 2), dtype=torch.float64, device=dev)
+    flow12 = torch.empty((h, w, 2), dtype=torch.float64, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws = _warp_workspace(lib, dev, h, w)
+        st = lib.snerf_warp_project(_ptr(depth1), _ptr(camera), _ptr(mask1), h, w, _ptr(points), _ptr(keys), _ptr(stats), _ptr(flow12),
+                                    _ptr(ws), _stream())
+    _lib.check(st, 'snerf_warp_project')
+    return points, keys, stats, flow12
+
+
+def warp_positions_from_flow(flow12: Tensor, depth1: Tensor, mask1: Optional[Tensor] = None, flow12_mask: Optional[Tensor] = None):
+    """Padded positions ((flow_x + x) + 1, (flow_y + y) + 1) and Z = ``depth1`` of every source of a float64 (h,w,2) flow; ``depth1``
+    float32 or float64 (h,w); a source either mask drops goes to the discard list.  -> points (1,3,h,w), keys (1,h,w), stats (1,2)."""
+    flow12 = _typed(flow12, 'flow12', (torch.float64,))
+    if flow12.dim() != 3 or flow12.shape[2] != 2:
+        raise RuntimeError(f'flow12: expected shape (h, w, 2), got {tuple(flow12.shape)}')
+    h, w = int(flow12.shape[0]), int(flow12.shape[1])
+    _visibility_extent(1, h, w, 'flow12')
+    depth1 = _typed(depth1, 'depth1', (torch.float32, torch.float64), (h, w))
+    mask1 = _warp_mask(mask1, 'mask1', h, w)
+    flow12_mask = _warp_mask(flow12_mask, 'flow12_mask', h, w)
+    dev = flow12.device
+    _warp_together(dev, depth1=depth1, mask1=mask1, flow12_mask=flow12_mask)
+    points = torch.empty((1, 3, h, w), dtype=torch.float64, device=dev)
+    keys = torch.empty((1, h, w), dtype=torch.int32, device=dev)
+    stats = torch.empty((1, 2), dtype=torch.float64, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws = _warp_workspace(lib, dev, h, w)
+        st = lib.snerf_warp_positions_from_flow(_ptr(flow12), _ptr(depth1), _WARP_TYPES[depth1.dtype], _ptr(mask1), _ptr(flow12_mask), h, w,
+                                                _ptr(points), _ptr(keys), _ptr(stats), _ptr(ws), _stream())
+    _lib.check(st, 'snerf_warp_positions_from_flow')
+    return points, keys, stats
+
+
+def warp_splat_gather(points: Tensor, order: Tensor, starts: Tensor, stats: Tensor, values: Tensor, is_image: bool = False):
+    """Splat the (h,w,c) ``values`` (uint8 with ``is_image``, float32 / float64 without) of the sources of ``points`` (1,3,h,w) through
+    the inverted index (``order``: the int64 permutation of the STABLE sort of the keys, ``starts``: visibility_mask_list_starts with
+    views = 1).  -> (warped (h,w,c) uint8 / float64, mask2 bool (h,w))."""
+    points = _typed(points, 'points', (torch.float64,))
+    if points.dim() != 4 or points.shape[0] != 1 or points.shape[1] != 3:
+        raise RuntimeError(f'points: expected shape (1, 3, h, w), got {tuple(points.shape)}')
+    h, w = int(points.shape[2]), int(points.shape[3])
+    per_view = _visibility_extent(1, h, w, 'points')
+    order = _typed(order, 'order', (torch.int64,), (h * w,))
+    starts = _typed(starts, 'starts', (torch.int32,), (per_view + 1,))
+    stats = _typed(stats, 'stats', (torch.float64,), (1, 2))
+    values, _, _, c = _warp_frame(values, 'values', is_image, (h, w))
+    dev = points.device
+    _warp_together(dev, order=order, starts=starts, stats=stats, values=values)
+    warped = torch.empty((h, w, c), dtype=torch.uint8 if is_image else torch.float64, device=dev)
+    mask2 = torch.empty((h, w), dtype=torch.bool, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        st = lib.snerf_warp_splat_gather(_ptr(points), _ptr(order), _ptr(starts), _ptr(stats), _ptr(values), _WARP_TYPES[values.dtype], c,
+                                         int(bool(is_image)), h, w, _ptr(warped), _ptr(mask2), _stream())
+    _lib.check(st, 'snerf_warp_splat_gather')
+    return warped, mask2
+
+
+def warp_interpolate(frame2: Tensor, flow12: Tensor, mask2: Optional[Tensor] = None, flow12_mask: Optional[Tensor] = None,
+                     is_image: bool = False):
+    """The backward warp of the (h,w,c) ``frame2`` along the float64 (h,w,2) ``flow12``.  -> (warped (h,w,c) uint8 / float64, mask1 bool)."""
+    frame2, h, w, c = _warp_frame(frame2, 'frame2', is_image)
+    flow12 = _typed(flow12, 'flow12', (torch.float64,), (h, w, 2))
+    mask2 = _warp_mask(mask2, 'mask2', h, w)
+    flow12_mask = _warp_mask(flow12_mask, 'flow12_mask', h, w)
+    dev = frame2.device
+    _warp_together(dev, flow12=flow12, mask2=mask2, flow12_mask=flow12_mask)
+    warped = torch.empty((h, w, c), dtype=torch.uint8 if is_image else torch.float64, device=dev)
+    mask1 = torch.empty((h, w), dtype=torch.bool, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        st = lib.snerf_warp_interpolate(_ptr(frame2), _WARP_TYPES[frame2.dtype], c, _ptr(mask2), _ptr(flow12), _ptr(flow12_mask),
+                                        int(bool(is_image)), h, w, _ptr(warped), _ptr(mask1), _stream())
+    _lib.check(st, 'snerf_warp_interpolate')
+    return warped, mask1
+
+
 # ---------------------------------------------------------------------------------------------- f1 losses
 class LossTermSpec:
     """One masked mean-squared-error term of the fused loss evaluation (struct snerf_loss_term).  ``two_sided``: the

@@ -23,6 +23,8 @@ backbone.
 
 The masks of the masked metrics are the stage's own first step (``src/qa/00_Common/src/mask_generators``): ``visibility_mask``
 splats the training views' depths into the test view and tests them against its depth, on the device (csrc/visibility_mask.hip).
+The Warper behind them is a utility of its own too: ``forward_warp`` (colour frame, mask, depth and flow), ``bilinear_splatting``
+along any flow and ``bilinear_interpolation``, the backward warp (csrc/warp.hip), pinned to tests/warp_reference.py.
 """
 from __future__ import annotations
 
@@ -214,6 +216,86 @@ def visibility_mask(depth_train: Tensor, depth_test: Tensor, extrinsics_train, e
     mask_views = gathered[0] if return_views else gathered
     mask = ops.visibility_mask_combine(mask_views, int(min_views))
     return (mask, mask_views.bool(), gathered[1], gathered[2]) if return_views else mask
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the reference's Warper as a utility of its own (src/qa/00_Common/src/mask_generators/Warper.py): csrc/warp.hip
+def _splat_index(keys: Tensor, h: int, w: int, library: bool):
+    """(order, starts) of one frame's splat keys: the stable sort (torch's or the library's) and the list starts."""
+    if library:
+        key_bits = max(1, (ops._visibility_extent(1, h, w, 'keys') - 1).bit_length())
+        sorted_keys, order = ops.sort_keys_with_order(keys.reshape(-1), key_bits)
+    else:
+        sorted_keys, order = torch.sort(keys.reshape(-1), stable=True)     # every list in ascending source order
+    return order, ops.visibility_mask_list_starts(sorted_keys, 1, h, w)
+
+
+def forward_warp(frame1: Tensor, depth1: Tensor, extrinsic1, extrinsic2, intrinsic1, intrinsic2=None, mask1: Optional[Tensor] = None,
+                 sorter: str = 'torch'):
+    """``Warper.forward_warp`` on the device: view 1's frame and depth splatted into view 2 (bilinear proximity x depth weight
+    1 / exp(50 L / max L), L = log(1 + clip(Z, 0, 1000)) of the transformed depth Z).
+
+    ``frame1`` uint8 (h,w,3) and ``depth1`` float32 (h,w) on the GPU, ``mask1`` bool (h,w) on the GPU or None (pixels where it is false
+    are ignored); extrinsics (4,4) world-to-camera and intrinsics (3,3), numpy or tensor (``intrinsic2`` None: ``intrinsic1``).
+    Returns, on the device, ``(warped_frame2 uint8 (h,w,3), mask2 bool (h,w), warped_depth2 float64 (h,w), flow12 float64 (h,w,2))``:
+    the colour clipped to [0, 255] and rounded half to even, True where something landed, the splatted Z (0 elsewhere), and the
+    flow (q0 / q2 - x, q1 / q2 - y) of every pixel of view 1.  The two splats share one projection, one sort and one list-start
+    pass; ``warped_depth2`` and ``mask2`` are, bit for bit, what ``visibility_mask`` computes for the same view (without a ``mask1``).
+    Arithmetic is fp64 and free of atomics: the same input gives the same bits.  As in the reference a point behind camera 2 still
+    splats, with the largest weight, and max L is taken over every pixel, masked ones included.  Not pinned by the reference
+    (undefined there) and given no contribution here: a source whose projection is not finite or leaves int32, and a view whose
+    depths give max L = 0.  ``sorter``: as for ``visibility_mask``; the outputs are the same bits either way."""
+    library = _sorter(sorter)
+    frame1, h, w, c = ops._warp_frame(frame1, 'frame1', True)
+    if c != 3:
+        raise RuntimeError(f'frame1: expected shape (h, w, 3), got {tuple(frame1.shape)}')
+    depth1 = ops._typed(depth1, 'depth1', (torch.float32,), (h, w))
+    mask1 = ops._warp_mask(mask1, 'mask1', h, w)
+    ops._warp_together(frame1.device, depth1=depth1, mask1=mask1)
+    cameras = visibility_cameras(_matrices(extrinsic1, 'extrinsic1', (4, 4))[None], _matrices(extrinsic2, 'extrinsic2', (4, 4)),
+                                 _matrices(intrinsic1, 'intrinsic1', (3, 3))[None],
+                                 None if intrinsic2 is None else _matrices(intrinsic2, 'intrinsic2', (3, 3)))
+    points, keys, stats, flow12 = ops.warp_project(depth1, torch.from_numpy(cameras[0]).to(depth1.device), mask1)
+    order, starts = _splat_index(keys, h, w, library)
+    warped_frame2, mask2 = ops.warp_splat_gather(points, order, starts, stats, frame1, is_image=True)
+    warped_depth2, _ = ops.warp_splat_gather(points, order, starts, stats, points[0, 2].unsqueeze(-1))     # Z splats itself
+    return warped_frame2, mask2, warped_depth2[:, :, 0], flow12
+
+
+def bilinear_splatting(frame1: Tensor, depth1: Tensor, flow12: Tensor, mask1: Optional[Tensor] = None,
+                       flow12_mask: Optional[Tensor] = None, is_image: bool = False, sorter: str = 'torch'):
+    """``Warper.bilinear_splatting`` on the device: ``frame1`` (h,w,c), c in 1..4, splatted along ``flow12`` float64 (h,w,2) with the
+    depth weights of ``depth1`` float32 or float64 (h,w) -- every source adds its value to the (up to) four cells around
+    (x + flow_x, y + flow_y).  ``mask1`` / ``flow12_mask`` bool (h,w) or None: a source where either is false adds nothing, but still
+    counts in max L, as in the reference.  ``is_image``: ``frame1`` is uint8 and so is the result (clipped to [0, 255], rounded half
+    to even); without it ``frame1`` is float32 or float64 and the result float64.  Returns ``(warped (h,w,c), mask2 bool (h,w))`` on
+    the device: sum v weight / sum weight where something landed, else 0.  fp64, no atomics, the same bits on every call; the
+    positions are numpy's bit for bit.  A float32 ``depth1`` is widened first (handed one, the reference computes its depth weights in
+    float32; ``forward_warp``'s own depth is float64).  Not pinned by the reference (undefined there) and given no contribution here: a source
+    whose position or depth is not finite or leaves int32, and a ``depth1`` whose max L is 0.  ``sorter``: as for
+    ``visibility_mask``."""
+    library = _sorter(sorter)
+    frame1, h, w, _ = ops._warp_frame(frame1, 'frame1', bool(is_image))
+    depth1 = ops._typed(depth1, 'depth1', (torch.float32, torch.float64), (h, w))
+    flow12 = ops._typed(flow12, 'flow12', (torch.float64,), (h, w, 2))
+    mask1 = ops._warp_mask(mask1, 'mask1', h, w)
+    flow12_mask = ops._warp_mask(flow12_mask, 'flow12_mask', h, w)
+    ops._warp_together(frame1.device, depth1=depth1, flow12=flow12, mask1=mask1, flow12_mask=flow12_mask)
+    points, keys, stats = ops.warp_positions_from_flow(flow12, depth1, mask1, flow12_mask)
+    order, starts = _splat_index(keys, h, w, library)
+    return ops.warp_splat_gather(points, order, starts, stats, frame1, is_image=bool(is_image))
+
+
+def bilinear_interpolation(frame2: Tensor, flow12: Tensor, mask2: Optional[Tensor] = None, flow12_mask: Optional[Tensor] = None,
+                           is_image: bool = False):
+    """``Warper.bilinear_interpolation`` on the device, the backward warp: pixel (x, y) of the result reads ``frame2`` (h,w,c), c in
+    1..4, at (x + flow_x, y + flow_y) (``flow12`` float64 (h,w,2)) through four bilinear taps of the frame padded by one cell of
+    zeros; ``mask2`` bool (h,w) or None marks the known pixels of ``frame2``, ``flow12_mask`` the valid flows.  dtypes and
+    ``is_image`` as for ``bilinear_splatting``.  Returns ``(warped (h,w,c), mask1 bool (h,w))`` on the device: nr / dr where the
+    weight dr of the known taps is positive, else 0.  Every pixel is independent and the operations keep the reference's order, so
+    the float64 result is numpy's bit for bit.  Not pinned by the reference (undefined there): a pixel whose position is not finite
+    or leaves int32 reads nothing (0, mask False); with ``is_image`` a NaN value is stored as 0."""
+    return ops.warp_interpolate(frame2, flow12, mask2, flow12_mask, bool(is_image))
 
 
 # ---------------------------------------------------------------------------------------------------------------
