@@ -367,6 +367,48 @@ int snerf_render_backward(const snerf_render_config* cfg, const snerf_render_mlp
                           long long num_rays, const snerf_render_outputs* out, const snerf_render_level_grads* grads,
                           float* workspace, snerf_stream_t stream);
 
+/* The output layout of a render call (added within ABI version 10): which outputs exist, their shapes, and where each one
+ * lies in the two pools a caller allocates -- every per-ray output of every level in one buffer, every per-sample output in
+ * another.  Host arithmetic only (csrc/render_layout.h); no device is touched.  Every pooled output is (n, dims...) row-major and
+ * all sizes are in floats PER RAY, so a layout holds for any ray count: an output begins n * unit_offset floats into its pool,
+ * and a pool holds n * pool_unit_floats floats. */
+enum snerf_render_field {                   /* the fields of snerf_render_level_out, in declaration order */
+    SNERF_FIELD_RGB = 0, SNERF_FIELD_ACC, SNERF_FIELD_DEPTH, SNERF_FIELD_DEPTH_VAR, SNERF_FIELD_DEPTH_NDC,
+    SNERF_FIELD_DEPTH_VAR_NDC, SNERF_FIELD_ALPHA, SNERF_FIELD_VISIBILITY, SNERF_FIELD_WEIGHTS, SNERF_FIELD_SIGMA,
+    SNERF_FIELD_RAW_RGB, SNERF_FIELD_SAVED_ACTS, SNERF_FIELD_RAW_VISIBILITY, SNERF_FIELD_RAW_VISIBILITY2,
+    SNERF_FIELD_VISIBILITY2, SNERF_FIELD_VIEW_DIRS2
+};
+#define SNERF_RENDER_FIELDS 16
+enum snerf_render_pool { SNERF_POOL_PER_RAY = 0, SNERF_POOL_PER_SAMPLE = 1, SNERF_POOL_OWN = 2 };
+
+typedef struct snerf_render_slot {
+    long long unit_offset;                  /* floats per ray from the start of its pool (0 for SNERF_POOL_OWN) */
+    int present;                            /* != 0: the call produces (or needs room for) this output */
+    int returned;                           /* != 0: the caller sees it; 0: scratch (view_dirs2, the weights carved only because
+                                               visibility2 is composited with them) and saved_acts */
+    int pool;                               /* enum snerf_render_pool; SNERF_POOL_OWN (saved_acts): an allocation of its own of
+                                               snerf_mlp_saved_floats floats, not linear in n */
+    int rank;                               /* trailing dimensions after n: 0..3 */
+    int dims[3];
+} snerf_render_slot;
+
+typedef struct snerf_render_layout {
+    int num_fine;                           /* cfg.num_fine, or 0 when the main fine level is absent */
+    int samples[SNERF_RENDER_LEVELS];       /* S of each level */
+    int needs_workspace;                    /* != 0: snerf_render_forward needs snerf_render_workspace_floats of scratch */
+    long long pool_unit_floats[2];          /* per-ray pool, per-sample pool */
+    snerf_render_slot depths_coarse, depths_fine;   /* depths_fine is absent without a fine pass or when the caller supplies it */
+    snerf_render_slot level[SNERF_RENDER_LEVELS][SNERF_RENDER_FIELDS];
+} snerf_render_layout;
+
+/* Of `mlps` only desc != NULL and desc->predict_visibility are read.  per_sample_mask: 1 alpha | 2 visibility | 4 weights.
+ * fine_depths_given != 0: the call passes rays.depths_fine. */
+int snerf_render_layout_query(const snerf_render_config* cfg, const snerf_render_mlp* mlps, int num_other, int per_sample_mask,
+                              int fine_depths_given, snerf_render_layout* layout);
+/* Points every pooled output of `out` into the two pools; absent outputs and saved_acts become NULL. */
+int snerf_render_layout_bind(const snerf_render_layout* layout, long long num_rays, float* per_ray_pool, float* per_sample_pool,
+                             snerf_render_outputs* out);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Output post-processing (next-row f3).  Replaces post_process_image / post_process_depth
  * (src/data_preprocessors/DataPreprocessor01.py:1106-1114) on the device, so a rendered frame crosses PCIe as uint8.

@@ -75,6 +75,19 @@ class RenderOutputs(ctypes.Structure):
     _fields_ = [('depths_coarse', c_void_p), ('depths_fine', c_void_p), ('level', RenderLevelOut * RENDER_LEVELS)]
 
 
+class RenderSlot(ctypes.Structure):
+    """struct snerf_render_slot"""
+    _fields_ = [('unit_offset', c_longlong), ('present', c_int), ('returned', c_int), ('pool', c_int), ('rank', c_int),
+                ('dims', c_int * 3)]
+
+
+class RenderLayout(ctypes.Structure):
+    """struct snerf_render_layout"""
+    _fields_ = [('num_fine', c_int), ('samples', c_int * RENDER_LEVELS), ('needs_workspace', c_int),
+                ('pool_unit_floats', c_longlong * 2), ('depths_coarse', RenderSlot), ('depths_fine', RenderSlot),
+                ('level', RenderSlot * len(LEVEL_OUT_FIELDS) * RENDER_LEVELS)]
+
+
 class RenderLevelGrads(ctypes.Structure):
     """struct snerf_render_level_grads"""
     _fields_ = [(name, c_void_p) for name in ('rgb', 'acc', 'depth', 'depth_ndc', 'sigma', 'raw_rgb')] + \
@@ -117,6 +130,8 @@ SIGNATURES = {
     'snerf_render_workspace_floats': (c_size_t, [POINTER(RenderConfig), c_longlong]),
     'snerf_render_forward': (c_int, [POINTER(RenderConfig), POINTER(RenderMlp), POINTER(RenderRays), c_longlong,
                                      POINTER(RenderOutputs), _FP, c_void_p]),
+    'snerf_render_layout_query': (c_int, [POINTER(RenderConfig), POINTER(RenderMlp), c_int, c_int, c_int, POINTER(RenderLayout)]),
+    'snerf_render_layout_bind': (c_int, [POINTER(RenderLayout), c_longlong, _FP, _FP, POINTER(RenderOutputs)]),
     'snerf_render_backward_workspace_floats': (c_size_t, [POINTER(RenderConfig), POINTER(RenderMlp), c_longlong]),
     'snerf_render_backward': (c_int, [POINTER(RenderConfig), POINTER(RenderMlp), POINTER(RenderRays), c_longlong,
                                       POINTER(RenderOutputs), POINTER(RenderLevelGrads), _FP, c_void_p]),

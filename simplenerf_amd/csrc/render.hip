@@ -7,6 +7,7 @@
 #include <mutex>
 #include <utility>
 
+#include "render_layout.h"
 #include "snerf_common.h"
 
 namespace snerf {   // render_fused.hip: the whole eval-mode render of a plain coarse + fine model as one launch
@@ -149,6 +150,20 @@ extern "C" size_t snerf_render_workspace_floats(const snerf_render_config* cfg, 
     return (size_t)num_rays * (size_t)cfg->num_coarse;
 }
 
+extern "C" int snerf_render_layout_query(const snerf_render_config* cfg, const snerf_render_mlp* mlps, int num_other,
+                                         int per_sample_mask, int fine_depths_given, snerf_render_layout* layout) {
+    const char* wrong = snerf::renderlayout::query(cfg, mlps, num_other, per_sample_mask, fine_depths_given != 0, layout);
+    SNERF_REQUIRE(!wrong, "render_layout_query: %s", wrong);
+    return SNERF_OK;
+}
+
+extern "C" int snerf_render_layout_bind(const snerf_render_layout* layout, long long num_rays, float* per_ray_pool,
+                                        float* per_sample_pool, snerf_render_outputs* out) {
+    SNERF_REQUIRE(layout && out && num_rays >= 0, "render_layout_bind: NULL argument or negative ray count");
+    snerf::renderlayout::bind(layout, num_rays, per_ray_pool, per_sample_pool, out);
+    return SNERF_OK;
+}
+
 extern "C" int snerf_render_forward(const snerf_render_config* cfg, const snerf_render_mlp* mlps, const snerf_render_rays* rays,
                                     long long num_rays, const snerf_render_outputs* out, float* workspace,
                                     snerf_stream_t stream) {
@@ -256,7 +271,7 @@ extern "C" int snerf_render_forward(const snerf_render_config* cfg, const snerf_
     }
     for (int l = 3; l < SNERF_RENDER_LEVELS; ++l) {
         if (!mlps[l].desc) continue;
-        rc = shade(l, depths_fine, cfg->num_coarse + cfg->num_fine, stream);
+        rc = shade(l, depths_fine, snerf::renderlayout::samples(cfg, l), stream);
         if (rc != SNERF_OK) return done(rc);
     }
     return done(SNERF_OK);
@@ -268,7 +283,7 @@ extern "C" size_t snerf_render_backward_workspace_floats(const snerf_render_conf
     size_t samples = 0, inner = 0, every = 0;
     for (int l = 0; l < SNERF_RENDER_LEVELS; ++l) {
         if (!mlps[l].desc) continue;
-        const int s = l < 3 ? cfg->num_coarse : cfg->num_coarse + cfg->num_fine;
+        const int s = snerf::renderlayout::samples(cfg, l);
         const size_t level_inner = snerf_mlp_backward_workspace_floats(mlps[l].desc, num_rays, s);
         samples = std::max(samples, (size_t)num_rays * (size_t)s);
         inner = std::max(inner, level_inner);
@@ -291,11 +306,11 @@ extern "C" int snerf_render_backward(const snerf_render_config* cfg, const snerf
     const float* march_d = cfg->ndc ? rays->rays_d_ndc : rays->rays_d;
     size_t samples_max = 0;
     for (int l = 0; l < SNERF_RENDER_LEVELS; ++l)
-        if (mlps[l].desc) samples_max = std::max(samples_max, (size_t)n * (size_t)(l < 3 ? cfg->num_coarse : cfg->num_coarse + cfg->num_fine));
+        if (mlps[l].desc) samples_max = std::max(samples_max, (size_t)n * (size_t)snerf::renderlayout::samples(cfg, l));
     // one level's backward on `s`: compositing backward (K6) -> raw-output gradients added -> MLP backward (K7)
     auto level_backward = [&](int l, float* d_sigma, float* d_rgb, float* inner, snerf_stream_t s_l) -> int {
         const snerf_render_level_grads& g = grads[l];
-        const int s = l < 3 ? cfg->num_coarse : cfg->num_coarse + cfg->num_fine;
+        const int s = snerf::renderlayout::samples(cfg, l);
         const float* depths = l < 3 ? out->depths_coarse : (rays->depths_fine ? rays->depths_fine : out->depths_fine);
         const snerf_render_level_out& o = out->level[l];
         int st = snerf_composite_backward(o.sigma, o.raw_rgb, depths, march_d, cfg->ndc ? rays->rays_o : nullptr,
@@ -347,7 +362,7 @@ extern "C" int snerf_render_backward(const snerf_render_config* cfg, const snerf
     size_t samples_of[SNERF_RENDER_LEVELS] = {};
     for (int l = 0; l < SNERF_RENDER_LEVELS; ++l) {
         if (!mlps[l].desc) continue;
-        const int s_l = l < 3 ? cfg->num_coarse : cfg->num_coarse + cfg->num_fine;
+        const int s_l = snerf::renderlayout::samples(cfg, l);
         samples_of[l] = (size_t)n * (size_t)s_l;
         d_sigma_of[l] = region;
         region += 4 * samples_of[l] + (snerf_mlp_backward_workspace_floats(mlps[l].desc, n, s_l) + 63) / 64 * 64;

@@ -15,6 +15,7 @@
 #include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <c10/util/accumulate.h>
+#include <c10/util/strides.h>
 #include <torch/csrc/autograd/custom_function.h>
 #include <torch/custom_class.h>
 #include <torch/library.h>
@@ -81,49 +82,40 @@ struct RenderCall {
     bool present[kLevels]{};
     snerf_render_rays rays{};
     snerf_render_outputs out{};
+    snerf_render_layout layout{};      // which outputs there are and where they lie in the pools (snerf_render_layout_query)
     long long n = 0;
-    int per_sample = 0;
-    int num_other = 0;
     std::vector<Tensor> held;          // inputs, pools, saved activations: the memory behind the pointers above
     std::vector<int> num_params;       // per level
-    struct DiffOutput { int index, level, key; };
-    std::vector<DiffOutput> diff_outputs;          // position, level and key of every differentiable output
+    struct DiffOutput { int index, level, field; };
+    std::vector<DiffOutput> diff_outputs;          // position, level and snerf_render_field of every differentiable output
     bool return_param_grads = false;
     c10::DeviceIndex device = 0;
-
-    int samples(int level) const { return level < 3 ? cfg.num_coarse : cfg.num_coarse + cfg.num_fine; }
 };
 
-enum Key { K_RGB, K_ACC, K_DEPTH, K_DEPTH_VAR, K_DEPTH_NDC, K_DEPTH_VAR_NDC, K_ALPHA, K_VISIBILITY, K_WEIGHTS, K_SIGMA, K_RAW_RGB,
-           K_RAW_VIS, K_RAW_VIS2, K_VIS2, kKeys };
-bool differentiable(int key) { return key == K_RGB || key == K_ACC || key == K_DEPTH || key == K_DEPTH_NDC || key == K_SIGMA || key == K_RAW_RGB; }
+bool differentiable(int field) {
+    return field == SNERF_FIELD_RGB || field == SNERF_FIELD_ACC || field == SNERF_FIELD_DEPTH || field == SNERF_FIELD_DEPTH_NDC ||
+           field == SNERF_FIELD_SIGMA || field == SNERF_FIELD_RAW_RGB;
+}
 
-struct Pool {
-    Tensor buffer;
-    int64_t used = 0;
-    Tensor carve(at::IntArrayRef shape) {
-        int64_t size = 1;
-        std::vector<int64_t> strides(shape.size());
-        for (int i = (int)shape.size() - 1; i >= 0; --i) { strides[i] = size; size *= shape[i]; }
-        Tensor view = buffer.as_strided(shape, strides, used);
-        used += size;
-        return view;
-    }
-};
+// (n, dims...) of a slot of the layout
+std::vector<int64_t> slot_shape(const snerf_render_slot& slot, int64_t n) {
+    std::vector<int64_t> shape{n};
+    shape.insert(shape.end(), slot.dims, slot.dims + slot.rank);
+    return shape;
+}
 
 // The forward proper: validates, allocates, fills the C structs, enqueues snerf_render_forward on the current stream.
 // Returns the output tensors: z_vals_coarse, z_vals_fine (when the model has a fine pass), then for every present level, in
-// level order, the defined keys in `Key` order.  `layout` receives (level, key) of every per-level output.
+// level order, the slots of the layout the caller sees, in field order.  `fields` receives (level, field) of each of those.
 std::vector<Tensor> run_forward(RenderCall& c, at::IntArrayRef cfg, at::IntArrayRef descs, const c10::List<std::optional<Tensor>>& packed,
                                 const c10::List<std::optional<Tensor>>& rays, const c10::List<std::optional<Tensor>>& draws,
-                                bool keep_activations, std::vector<std::pair<int, int>>* layout) {
+                                bool keep_activations, std::vector<std::pair<int, int>>* fields) {
     TORCH_CHECK((int)cfg.size() == kCfgInts, "snerf::render: cfg holds ", kCfgInts, " ints, got ", cfg.size());
     TORCH_CHECK((int)descs.size() == kLevels * kDescInts, "snerf::render: descs holds ", kLevels * kDescInts, " ints, got ", descs.size());
     TORCH_CHECK((int)packed.size() == kLevels && (int)rays.size() == kRays && (int)draws.size() == kDraws,
                 "snerf::render: packed / rays / draws hold ", kLevels, " / ", (int)kRays, " / ", (int)kDraws, " entries");
     c.cfg.ndc = (int)cfg[0]; c.cfg.white_bkgd = (int)cfg[1]; c.cfg.lindisp = (int)cfg[2]; c.cfg.num_coarse = (int)cfg[3];
     c.cfg.num_fine = (int)cfg[4]; c.cfg.precision = (int)cfg[5]; c.cfg.keep_activations = keep_activations ? 1 : 0;
-    c.per_sample = (int)cfg[6];
     c.cfg.fused = (int)cfg[7] && !keep_activations ? 1 : 0;
     const bool ndc = c.cfg.ndc != 0;
     const std::optional<Tensor> rays_o = rays.get(R_O);
@@ -148,113 +140,63 @@ std::vector<Tensor> run_forward(RenderCall& c, at::IntArrayRef cfg, at::IntArray
             c.mlps[l].packed = hold(*p).data_ptr<float>();
         }
     }
-    TORCH_CHECK(c.present[0], "snerf::render: the main coarse MLP is required");
-    if (!c.present[3]) c.cfg.num_fine = 0;
-    const int s_c = c.cfg.num_coarse, s_f = c.cfg.num_fine;
-
-    snerf_render_rays& r = c.rays;
     // (presence is checked on the tensors, not the pointers: a zero-ray call has tensors without storage)
-    auto given = [&](int index) { const std::optional<Tensor> t = rays.get(index); return t.has_value() && t->defined(); };
-    r.rays_o = ptr(hold(operand(rays.get(R_O), "rays_o", {n, 3})));
-    r.rays_d = ptr(hold(operand(rays.get(R_D), "rays_d", {n, 3})));
-    TORCH_CHECK(given(R_D), "snerf::render: rays_d is required");
+    auto given = [](const std::optional<Tensor>& t) { return t.has_value() && t->defined(); };
     bool need_dirs = false, predicts = false;
     for (int l = 0; l < kLevels; ++l) {
         need_dirs = need_dirs || (c.present[l] && c.descs[l].use_view_dirs);
         predicts = predicts || (c.present[l] && c.descs[l].predict_visibility);
     }
+    const std::optional<Tensor> o2 = rays.get(R_O2);
+    const bool secondary = predicts && given(o2);
+    TORCH_CHECK(!secondary || o2->dim() == 3, "rays_o2: expected (n, K, 3)");
+    const int k_other = secondary ? (int)o2->size(1) : 0;
+    snerf_render_layout& lay = c.layout;
+    check_status(snerf_render_layout_query(&c.cfg, c.mlps, k_other, (int)cfg[6], given(draws.get(D_ZFINE)), &lay), "snerf_render_layout_query");
+    c.cfg.num_fine = lay.num_fine;
+    const int s_f = lay.num_fine;
+
+    snerf_render_rays& r = c.rays;
+    r.rays_o = ptr(hold(operand(rays.get(R_O), "rays_o", {n, 3})));
+    r.rays_d = ptr(hold(operand(rays.get(R_D), "rays_d", {n, 3})));
+    TORCH_CHECK(given(rays.get(R_D)), "snerf::render: rays_d is required");
     r.view_dirs = need_dirs ? ptr(hold(operand(rays.get(R_VIEW), "view_dirs", {n, 3}))) : nullptr;
-    TORCH_CHECK(!need_dirs || given(R_VIEW), "snerf::render: view_dirs is required (an MLP uses view directions)");
+    TORCH_CHECK(!need_dirs || given(rays.get(R_VIEW)), "snerf::render: view_dirs is required (an MLP uses view directions)");
     r.rays_o_ndc = ndc ? ptr(hold(operand(rays.get(R_O_NDC), "rays_o_ndc", {n, 3}))) : nullptr;
     r.rays_d_ndc = ndc ? ptr(hold(operand(rays.get(R_D_NDC), "rays_d_ndc", {n, 3}))) : nullptr;
-    TORCH_CHECK(!ndc || (given(R_O_NDC) && given(R_D_NDC)), "snerf::render: rays_o_ndc / rays_d_ndc are required when ndc");
+    TORCH_CHECK(!ndc || (given(rays.get(R_O_NDC)) && given(rays.get(R_D_NDC))), "snerf::render: rays_o_ndc / rays_d_ndc are required when ndc");
     r.near = ptr(hold(operand(rays.get(R_NEAR), "near", {n})));
     r.far = ptr(hold(operand(rays.get(R_FAR), "far", {n})));
-    TORCH_CHECK(given(R_NEAR) && given(R_FAR), "snerf::render: near / far are required");
-    r.t_rand = ptr(hold(operand(draws.get(D_TRAND), "t_rand", {n, s_c})));
+    TORCH_CHECK(given(rays.get(R_NEAR)) && given(rays.get(R_FAR)), "snerf::render: near / far are required");
+    r.t_rand = ptr(hold(operand(draws.get(D_TRAND), "t_rand", {n, lay.samples[0]})));
     r.u = s_f ? ptr(hold(operand(draws.get(D_U), "u", {n, s_f}))) : nullptr;
     for (int l = 0; l < kLevels; ++l)
-        r.sigma_noise[l] = c.present[l] ? ptr(hold(operand(draws.get(D_NOISE0 + l), "sigma_noise", {n, c.samples(l)}))) : nullptr;
-    Tensor fine_in = s_f ? operand(draws.get(D_ZFINE), "z_vals_fine", {n, s_c + s_f}) : Tensor();
+        r.sigma_noise[l] = c.present[l] ? ptr(hold(operand(draws.get(D_NOISE0 + l), "sigma_noise", {n, lay.samples[l]}))) : nullptr;
+    Tensor fine_in = s_f ? operand(draws.get(D_ZFINE), "z_vals_fine", {n, lay.samples[SNERF_LEVEL_MAIN_FINE]}) : Tensor();
     r.depths_fine = ptr(hold(fine_in));
-    Tensor rays_o2;
-    if (predicts) {
-        const std::optional<Tensor> o2 = rays.get(R_O2);
-        if (o2.has_value() && o2->defined()) {
-            TORCH_CHECK(o2->dim() == 3, "rays_o2: expected (n, K, 3)");
-            rays_o2 = operand(o2, "rays_o2", {n, o2->size(1), 3});
-        }
-    }
-    const int k_other = rays_o2.defined() ? (int)rays_o2.size(1) : 0;
-    r.rays_o2 = k_other ? ptr(hold(rays_o2)) : nullptr;
+    r.rays_o2 = k_other ? ptr(hold(operand(o2, "rays_o2", {n, k_other, 3}))) : nullptr;
     r.num_other = k_other;
-    c.num_other = k_other;
 
-    // ---- outputs: one allocation per group (per-ray, per-sample), views carved out of them
-    const bool want[3] = {(c.per_sample & 1) != 0, (c.per_sample & 2) != 0, (c.per_sample & 4) != 0};   // alpha, visibility, weights
-    const int per_ray_floats = 3 + 1 + 1 + 1 + (ndc ? 2 : 0);
-    int64_t ray_floats = 0, sample_floats = n * s_c + ((s_f && !fine_in.defined()) ? n * (s_c + s_f) : 0);
+    // ---- outputs: one allocation per pool (per-ray, per-sample), one view per slot of the layout the caller sees
+    const Tensor pools[2] = {hold(at::empty({n * (int64_t)lay.pool_unit_floats[0]}, options)), hold(at::empty({n * (int64_t)lay.pool_unit_floats[1]}, options))};
+    check_status(snerf_render_layout_bind(&lay, n, mptr(pools[0]), mptr(pools[1]), &c.out), "snerf_render_layout_bind");
+    auto view = [&](const snerf_render_slot& slot) {
+        const std::vector<int64_t> shape = slot_shape(slot, n);
+        return pools[slot.pool].as_strided(shape, c10::contiguous_strides(shape), n * slot.unit_offset);
+    };
+    std::vector<Tensor> outputs{view(lay.depths_coarse)};
+    if (s_f) outputs.push_back(lay.depths_fine.present ? view(lay.depths_fine) : fine_in);
     for (int l = 0; l < kLevels; ++l) {
-        if (!c.present[l]) continue;
-        const int64_t s = c.samples(l);
-        ray_floats += per_ray_floats * n;
-        sample_floats += n * s * (4 + (int)want[0] + (int)want[1] + (int)want[2]);
-        if (c.descs[l].predict_visibility) {
-            sample_floats += n * s * (1 + 4 * k_other + ((want[2] || !k_other) ? 0 : 1));
-            ray_floats += n * k_other;
+        for (int f = 0; f < SNERF_RENDER_FIELDS; ++f) {
+            if (!lay.level[l][f].returned) continue;
+            outputs.push_back(view(lay.level[l][f]));
+            fields->emplace_back(l, f);
         }
+        if (lay.level[l][SNERF_FIELD_SAVED_ACTS].present)
+            c.out.level[l].saved_acts = mptr(hold(at::empty({(int64_t)snerf_mlp_saved_floats(&c.descs[l], n, lay.samples[l])}, options)));
     }
-    Pool small{at::empty({ray_floats}, options)}, big{at::empty({sample_floats}, options)};
-    std::vector<Tensor> outputs;
-    snerf_render_outputs& o = c.out;
-    Tensor z_coarse = big.carve({n, s_c});
-    o.depths_coarse = mptr(z_coarse);
-    outputs.push_back(z_coarse);
-    o.depths_fine = nullptr;
-    if (s_f) {
-        Tensor z_fine = fine_in.defined() ? fine_in : big.carve({n, s_c + s_f});
-        if (!fine_in.defined()) o.depths_fine = mptr(z_fine);
-        outputs.push_back(z_fine);
-    }
-    for (int l = 0; l < kLevels; ++l) {
-        snerf_render_level_out& lo = o.level[l];
-        lo = snerf_render_level_out{};
-        if (!c.present[l]) continue;
-        const int64_t s = c.samples(l);
-        auto emit = [&](int key, const Tensor& t) { outputs.push_back(t); layout->emplace_back(l, key); return mptr(t); };
-        lo.rgb = emit(K_RGB, small.carve({n, 3}));
-        lo.acc = emit(K_ACC, small.carve({n}));
-        lo.depth = emit(K_DEPTH, small.carve({n}));
-        lo.depth_var = emit(K_DEPTH_VAR, small.carve({n}));
-        if (ndc) {
-            lo.depth_ndc = emit(K_DEPTH_NDC, small.carve({n}));
-            lo.depth_var_ndc = emit(K_DEPTH_VAR_NDC, small.carve({n}));
-        }
-        if (want[0]) lo.alpha = emit(K_ALPHA, big.carve({n, s}));
-        if (want[1]) lo.visibility = emit(K_VISIBILITY, big.carve({n, s}));
-        if (want[2]) lo.weights = emit(K_WEIGHTS, big.carve({n, s}));
-        lo.sigma = emit(K_SIGMA, big.carve({n, s, 1}));
-        lo.raw_rgb = emit(K_RAW_RGB, big.carve({n, s, 3}));
-        if (c.descs[l].predict_visibility) {
-            lo.raw_visibility = emit(K_RAW_VIS, big.carve({n, s, 1}));
-            if (k_other) {
-                lo.raw_visibility2 = emit(K_RAW_VIS2, big.carve({n, s, k_other, 1}));
-                lo.visibility2 = emit(K_VIS2, small.carve({n, k_other}));
-                lo.view_dirs2 = mptr(big.carve({n, s, k_other, 3}));
-                if (!lo.weights) lo.weights = mptr(big.carve({n, s}));   // visibility2 is composited with the level's weights
-            }
-        }
-        if (keep_activations) {
-            const int64_t floats = (int64_t)snerf_mlp_saved_floats(&c.descs[l], n, (int)s);
-            lo.saved_acts = mptr(hold(at::empty({floats}, options)));
-        }
-    }
-    TORCH_INTERNAL_ASSERT(small.used == ray_floats && big.used == sample_floats, "snerf::render: output pools mis-sized");
-    hold(small.buffer);
-    hold(big.buffer);
     Tensor work;
-    if (s_f && !fine_in.defined() && !want[2])
-        work = hold(at::empty({(int64_t)snerf_render_workspace_floats(&c.cfg, n)}, options));
+    if (lay.needs_workspace) work = hold(at::empty({(int64_t)snerf_render_workspace_floats(&c.cfg, n)}, options));
     if (n > 0) {
         const c10::hip::HIPGuard guard(c.device);
         hipStream_t stream = c10::hip::getCurrentHIPStream(c.device).stream();
@@ -271,13 +213,13 @@ struct RenderFunction : public torch::autograd::Function<RenderFunction> {
     static variable_list forward(AutogradContext* ctx, at::TensorList params, std::shared_ptr<RenderCall> call,
                                  std::vector<int64_t> cfg, std::vector<int64_t> descs, c10::List<std::optional<Tensor>> packed,
                                  c10::List<std::optional<Tensor>> rays, c10::List<std::optional<Tensor>> draws, bool keep) {
-        std::vector<std::pair<int, int>> layout;
-        std::vector<Tensor> outputs = run_forward(*call, cfg, descs, packed, rays, draws, keep, &layout);
-        const size_t first_level_output = outputs.size() - layout.size();
+        std::vector<std::pair<int, int>> fields;
+        std::vector<Tensor> outputs = run_forward(*call, cfg, descs, packed, rays, draws, keep, &fields);
+        const size_t first_level_output = outputs.size() - fields.size();
         variable_list plain;
         for (size_t i = 0; i < outputs.size(); ++i) {
-            if (i >= first_level_output && differentiable(layout[i - first_level_output].second))
-                call->diff_outputs.push_back({(int)i, layout[i - first_level_output].first, layout[i - first_level_output].second});
+            if (i >= first_level_output && differentiable(fields[i - first_level_output].second))
+                call->diff_outputs.push_back({(int)i, fields[i - first_level_output].first, fields[i - first_level_output].second});
             else
                 plain.push_back(outputs[i]);
         }
@@ -304,21 +246,19 @@ struct RenderFunction : public torch::autograd::Function<RenderFunction> {
         for (const RenderCall::DiffOutput& d : c.diff_outputs) {
             const Tensor& g = grad_outputs[d.index];
             if (!g.defined()) continue;
-            const int l = d.level, key = d.key;
-            const int64_t s = c.samples(l);
-            std::vector<int64_t> shape = key == K_RGB ? std::vector<int64_t>{n, 3} : key == K_SIGMA ? std::vector<int64_t>{n, s, 1}
-                                       : key == K_RAW_RGB ? std::vector<int64_t>{n, s, 3} : std::vector<int64_t>{n};
+            const int l = d.level, field = d.field;
+            const std::vector<int64_t> shape = slot_shape(c.layout.level[l][field], n);
             TORCH_CHECK(g.is_cuda() && g.scalar_type() == at::kFloat && g.numel() == c10::multiply_integers(shape),
-                        "snerf::render backward: unexpected gradient for output ", key, " of level ", l);
+                        "snerf::render backward: unexpected gradient for output ", field, " of level ", l);
             Tensor t = g.reshape(shape).contiguous();
             keep.push_back(t);
             const float* p = t.data_ptr<float>();
-            switch (key) {
-                case K_RGB: grads[l].rgb = p; break;
-                case K_ACC: grads[l].acc = p; break;
-                case K_DEPTH: grads[l].depth = p; break;
-                case K_DEPTH_NDC: grads[l].depth_ndc = p; break;
-                case K_SIGMA: grads[l].sigma = p; break;
+            switch (field) {
+                case SNERF_FIELD_RGB: grads[l].rgb = p; break;
+                case SNERF_FIELD_ACC: grads[l].acc = p; break;
+                case SNERF_FIELD_DEPTH: grads[l].depth = p; break;
+                case SNERF_FIELD_DEPTH_NDC: grads[l].depth_ndc = p; break;
+                case SNERF_FIELD_SIGMA: grads[l].sigma = p; break;
                 default: grads[l].raw_rgb = p; break;
             }
             any[l] = true;
@@ -381,7 +321,7 @@ struct RenderFunction : public torch::autograd::Function<RenderFunction> {
 
 // snerf::render(cfg, descs, packed, rays, draws, params, num_params, keep_activations, return_param_grads) -> Tensor[]
 // Output order: z_vals_coarse, z_vals_fine (if the model has a fine pass), then for every present level, in level order, the
-// keys it produces in the order of `Key`.  rgb, acc, depth, depth_ndc, sigma, raw_rgb carry the autograd node.
+// outputs the caller sees in the field order of snerf_render_level_out.  rgb, acc, depth, depth_ndc, sigma, raw_rgb carry the autograd node.
 std::vector<Tensor> render(at::IntArrayRef cfg, at::IntArrayRef descs, const c10::List<std::optional<Tensor>>& packed,
                            const c10::List<std::optional<Tensor>>& rays, const c10::List<std::optional<Tensor>>& draws,
                            at::TensorList params, at::IntArrayRef num_params, bool keep_activations, bool return_param_grads) {

@@ -259,7 +259,7 @@ class SimpleNeRFHip(torch.nn.Module):
         self.host_binding = mcfg.get('hip_host_binding', 'torch_ext')
         if self.host_binding not in ('torch_ext', 'ctypes'):
             raise KeyError(f"model.hip_host_binding must be 'torch_ext' or 'ctypes', got {self.host_binding!r}")
-        self._desc_ints: Dict[tuple, list] = {}
+        self._desc_ints: Dict[tuple, tuple] = {}
 
     # ------------------------------------------------------------------------------------------
     def set_random_draws(self, draws: Optional[dict]) -> None:
@@ -380,31 +380,27 @@ class SimpleNeRFHip(torch.nn.Module):
         z_fine = draws['z_vals_fine'] if 'z_vals_fine' in draws else (next(it) if self.fine_mlp_needed else None)
         return z_coarse, z_fine, out_levels
 
-    _EXT_KEYS = ('rgb', 'acc', 'depth', 'depth_var', 'depth_ndc', 'depth_var_ndc', 'alpha', 'visibility', 'weights', 'sigma',
-                 'raw_rgb', 'raw_visibility', 'raw_visibility2', 'visibility2')     # order of `enum Key` in snerf_torch.cpp
-
     def _render_with_extension(self, batch, draws, present, packed, s_c, s_f, per_sample, with_grad, returns):
         """torch.ops.snerf.render: one dispatcher call; validation, output allocation, pointer tables and the autograd node
         live in C++ (csrc_torch/snerf_torch.cpp)."""
         snerf = _torch_ext.load()
         mcfg = self.configs['model']
         key = tuple(present)
-        descs = self._desc_ints.get(key)
-        if descs is None:
+        if key not in self._desc_ints:
             descs = []
             for mlp in packed:
                 d = mlp.desc if mlp is not None else None
                 descs += [0] * 10 if d is None else [d.points_net_depth, d.points_net_width, d.views_net_depth, d.views_net_width,
                                                       d.points_pe_degree, d.views_pe_degree, d.sigma_pe_degree, d.use_view_dirs,
                                                       d.view_dependent_rgb, d.predict_visibility]
-            self._desc_ints[key] = descs
-        mask = (1 if 'alpha' in per_sample else 0) | (2 if 'visibility' in per_sample else 0) | (4 if 'weights' in per_sample else 0)
+            self._desc_ints[key] = descs, tuple(None if m is None else bool(m.desc.predict_visibility) for m in packed)
+        descs, predict = self._desc_ints[key]
+        mask = sum(ops.PER_SAMPLE_BITS[k] for k in per_sample)
         cfg = [int(self.ndc), int(bool(mcfg['white_bkgd'])), int(bool(mcfg['lindisp'])), s_c, s_f, self.precision, mask,
                int(self.fused_render)]
         near, far = (batch['near_ndc'], batch['far_ndc']) if self.ndc else (batch['near'], batch['far'])
-        predicts = any(m is not None and m.desc.predict_visibility for m in packed)
         rays = [batch['rays_o'], batch['rays_d'], batch.get('view_dirs'), batch.get('rays_o_ndc') if self.ndc else None,
-                batch.get('rays_d_ndc') if self.ndc else None, near, far, batch.get('rays_o2') if predicts else None]
+                batch.get('rays_d_ndc') if self.ndc else None, near, far, batch.get('rays_o2') if any(predict) else None]
         draw_list = [draws.get('t_rand'), draws.get('u')] + [draws.get(('noise', l)) for l in range(6)] + [draws.get('z_vals_fine')]
         params, counts = [], [0] * 6
         if with_grad:
@@ -423,23 +419,12 @@ class SimpleNeRFHip(torch.nn.Module):
         it = iter(res)
         z_coarse = next(it)
         z_fine = next(it) if self.fine_mlp_needed else None
-        k_other = rays[7].shape[1] if rays[7] is not None else 0
-        out_levels: Dict[int, Dict[str, Tensor]] = {}
-        for l, mlp in enumerate(packed):
-            if mlp is None:
-                continue
-            d = out_levels[l] = {}
-            vis = bool(mlp.desc.predict_visibility)
-            for k in self._EXT_KEYS:
-                if k in ('depth_ndc', 'depth_var_ndc') and not self.ndc:
-                    continue
-                if k in ('alpha', 'visibility', 'weights') and k not in per_sample:
-                    continue
-                if k == 'raw_visibility' and not vis:
-                    continue
-                if k in ('raw_visibility2', 'visibility2') and not (vis and k_other):
-                    continue
-                d[k] = next(it)
+        # the per-level outputs follow in the order of the call's layout (the library's snerf_render_layout, cached per configuration)
+        lay = ops.render_layout(self.ndc, s_c, s_f, with_grad, predict, rays[7].shape[1] if rays[7] is not None else 0, mask,
+                                draws.get('z_vals_fine') is not None)
+        out_levels: Dict[int, Dict[str, Tensor]] = {l: {} for l, mlp in enumerate(packed) if mlp is not None}
+        for l, name, _ in lay.returned:
+            out_levels[l][name] = next(it)
         return z_coarse, z_fine, out_levels
 
     # ------------------------------------------------------------------------------------------

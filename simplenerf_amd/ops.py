@@ -3,6 +3,8 @@ computation happens in the HIP library.  Inputs must be CUDA(HIP) float32 tensor
 from __future__ import annotations
 
 import ctypes
+import functools
+import math
 from typing import Dict, List, Optional
 
 import numpy
@@ -278,26 +280,57 @@ class PackedMlp:
 
 
 # ---------------------------------------------------------------------------------------------- one-call render ops
-def _row_major_strides(shape):
-    strides, step = [], 1
-    for d in reversed(shape):
-        strides.append(step)
-        step *= d
-    return tuple(reversed(strides))
+PER_SAMPLE_BITS = {'alpha': 1, 'visibility': 2, 'weights': 4}     # the per-sample request mask of snerf_render_layout_query
+
+
+class RenderLayout:
+    """A ``snerf_render_layout`` (csrc/render_layout.h owns the rules) read into plain Python once: it does not depend on the ray
+    count.  A slot is (pool, unit offset, trailing shape, strides of (n,) + trailing shape): pools[pool].as_strided((n,) + shape,
+    strides, n * offset) is the output."""
+
+    def __init__(self, c: _lib.RenderLayout):
+        self.c = c
+        self.samples, self.num_fine = tuple(c.samples), int(c.num_fine)
+        self.pool_unit_floats, self.needs_workspace = tuple(c.pool_unit_floats), bool(c.needs_workspace)
+        self.depths_coarse = self._slot(c.depths_coarse)
+        self.depths_fine = self._slot(c.depths_fine) if c.depths_fine.present else None
+        # (level, field name, slot) of every output the caller sees, in level and field order
+        self.returned = tuple((l, name, self._slot(c.level[l][f])) for l in range(_lib.RENDER_LEVELS)
+                              for f, name in enumerate(_lib.LEVEL_OUT_FIELDS) if c.level[l][f].returned)
+
+    @staticmethod
+    def _slot(slot):
+        dims = tuple(slot.dims[:slot.rank])
+        return slot.pool, int(slot.unit_offset), dims, tuple(math.prod(dims[i:]) for i in range(len(dims) + 1))
+
+
+@functools.lru_cache(maxsize=None)
+def render_layout(ndc: bool, num_coarse: int, num_fine: int, keep_activations: bool, levels: tuple, num_other: int,
+                  per_sample_mask: int, fine_depths_given: bool) -> RenderLayout:
+    """snerf_render_layout_query, cached per configuration.  ``levels``: per level None (absent) or whether its MLP predicts
+    visibility -- all the query reads of an MLP."""
+    cfg = _lib.RenderConfig(ndc=int(ndc), num_coarse=num_coarse, num_fine=num_fine, keep_activations=int(keep_activations))
+    descs = [None if v is None else MlpDesc(predict_visibility=int(v)) for v in levels]
+    mlps = (_lib.RenderMlp * _lib.RENDER_LEVELS)()
+    for l, d in enumerate(descs):
+        if d is not None:
+            mlps[l].desc = ctypes.pointer(d)
+    c = _lib.RenderLayout()
+    _lib.check(_lib.load().snerf_render_layout_query(ctypes.byref(cfg), mlps, num_other, per_sample_mask, int(fine_depths_given),
+                                                     ctypes.byref(c)), 'snerf_render_layout_query')
+    return RenderLayout(c)
 
 
 class RenderCall:
     """One ``snerf_render_forward`` (and, for training, its ``snerf_render_backward``): the whole of SimpleNeRF.render_rays
     (src/models/SimpleNeRF01.py:108-270) enqueued by ONE call into the library.  Output tensors are carved out of three
     allocations -- per-ray outputs, per-sample outputs, and (training) one saved-activation buffer per level -- instead
-    of ~20 separate ones.
+    of ~20 separate ones; which outputs there are and where they lie is the library's ``snerf_render_layout``.
 
     ``mlps``: six entries (C-ABI level order: main / points-aug / views-aug at the coarse level, then at the fine level),
     ``PackedMlp`` or None.  ``rays``: the reference's input_batch tensors.  ``draws``: t_rand, u, per-level sigma noise,
     optional fine-depth override.  ``per_sample``: which (n,S) composite outputs to produce ('alpha', 'visibility',
     'weights')."""
-
-    PER_RAY = (('rgb', 3), ('acc', 1), ('depth', 1), ('depth_var', 1), ('depth_ndc', 1), ('depth_var_ndc', 1))
 
     def __init__(self, mlps: List[Optional['PackedMlp']], ndc: bool, white_bkgd: bool, lindisp: bool, num_coarse: int,
                  num_fine: int, precision: int, keep_activations: bool, per_sample=('alpha',), fused: bool = False):
@@ -305,22 +338,18 @@ class RenderCall:
         self.lib = lib
         self.mlps = list(mlps) + [None] * (_lib.RENDER_LEVELS - len(mlps))
         self.ndc, self.keep = bool(ndc), bool(keep_activations)
-        self.num_coarse, self.num_fine = int(num_coarse), int(num_fine) if self.mlps[3] is not None else 0
-        self.cfg = _lib.RenderConfig(int(bool(ndc)), int(bool(white_bkgd)), int(bool(lindisp)), self.num_coarse, self.num_fine,
+        self.cfg = _lib.RenderConfig(int(bool(ndc)), int(bool(white_bkgd)), int(bool(lindisp)), int(num_coarse), int(num_fine),
                                      int(precision), int(self.keep), int(bool(fused) and not self.keep))
         self.c_mlps = (_lib.RenderMlp * _lib.RENDER_LEVELS)()
         for l, m in enumerate(self.mlps):
             if m is not None:
                 self.c_mlps[l].desc = ctypes.pointer(m.desc)
                 self.c_mlps[l].packed = m.buffer.data_ptr()
-        self.per_sample = tuple(per_sample)
+        self.per_sample_mask = sum(PER_SAMPLE_BITS[name] for name in set(per_sample))
         self.levels = [l for l, m in enumerate(self.mlps) if m is not None]
         self.c_rays = _lib.RenderRays()
         self.c_out = _lib.RenderOutputs()
         self.held: list = []      # tensors whose pointers sit in the structs
-
-    def samples(self, level: int) -> int:
-        return self.num_coarse if level < 3 else self.num_coarse + self.num_fine
 
     def forward(self, rays: Dict[str, Tensor], draws: Dict[str, Optional[Tensor]]):
         """-> (z_vals_coarse, z_vals_fine or None, {level: {name: tensor}})"""
@@ -330,6 +359,15 @@ class RenderCall:
         self.n, self.device = n, dev
         r = self.c_rays
         held = self.held = []
+        # predict_visibility: secondary camera centres (n, K, 3), K = num_frames - 1 (sec_views_vis)
+        predicts = tuple(None if m is None else bool(m.desc.predict_visibility) for m in self.mlps)
+        rays_o2 = rays.get('rays_o2') if any(predicts) else None
+        k_other = 0 if rays_o2 is None else int(rays_o2.shape[1])
+        override = draws.get('z_vals_fine')
+        lay = self.layout = render_layout(self.ndc, self.cfg.num_coarse, self.cfg.num_fine, self.keep, predicts, k_other,
+                                          self.per_sample_mask, override is not None)
+        self.cfg.num_fine = lay.num_fine
+        samples = lay.samples
 
         def put(name, t, shape):
             t = _dev(t, name, shape)
@@ -348,90 +386,37 @@ class RenderCall:
             r.rays_o_ndc = r.rays_d_ndc = 0
             near, far = rays['near'], rays['far']
         r.near, r.far = put('near', near.reshape(-1), (n,)), put('far', far.reshape(-1), (n,))
-        r.t_rand = put('t_rand', draws.get('t_rand'), (n, self.num_coarse))
-        r.u = put('u', draws.get('u'), (n, self.num_fine)) if self.num_fine else 0
+        r.t_rand = put('t_rand', draws.get('t_rand'), (n, samples[0]))
+        r.u = put('u', draws.get('u'), (n, lay.num_fine)) if lay.num_fine else 0
         for l in range(_lib.RENDER_LEVELS):
             noise = draws.get(('noise', l)) if l in self.levels else None
-            r.sigma_noise[l] = put('sigma_noise', None if noise is None else noise.reshape(n, self.samples(l)), (n, self.samples(l)))
-        override = draws.get('z_vals_fine') if self.num_fine else None
-        r.depths_fine = put('z_vals_fine', override, (n, self.num_coarse + self.num_fine))
+            r.sigma_noise[l] = put('sigma_noise', None if noise is None else noise.reshape(n, samples[l]), (n, samples[l]))
+        r.depths_fine = put('z_vals_fine', override if lay.num_fine else None, (n, samples[3]))
         fine_in = held[-1]        # the validated (contiguous fp32) override, or None: returned as z_vals_fine below
-        # predict_visibility: secondary camera centres (n, K, 3), K = num_frames - 1 (sec_views_vis)
-        rays_o2 = rays.get('rays_o2') if any(self.mlps[l].desc.predict_visibility for l in self.levels) else None
-        k_other = 0 if rays_o2 is None else int(rays_o2.shape[1])
         r.rays_o2 = put('rays_o2', rays_o2, (n, k_other, 3)) if k_other else 0
         r.num_other = k_other
 
-        # ---- outputs: one allocation per group, views carved out of it
-        per_ray = [(name, width) for name, width in self.PER_RAY if self.ndc or not name.endswith('_ndc')]
-        ray_floats = sum(w for _, w in per_ray) * n * len(self.levels)
-        sample_floats = n * self.num_coarse + (n * (self.num_coarse + self.num_fine) if self.num_fine and override is None else 0)
-        for l in self.levels:
-            sample_floats += n * self.samples(l) * (4 + len(self.per_sample))
-            if self.mlps[l].desc.predict_visibility:
-                want_weights = 0 if 'weights' in self.per_sample or not k_other else 1
-                sample_floats += n * self.samples(l) * (1 + 4 * k_other + want_weights)
-                ray_floats += n * k_other
-        small = torch.empty((ray_floats,), dtype=torch.float32, device=dev)
-        big = torch.empty((sample_floats,), dtype=torch.float32, device=dev)
-        pos = {'small': 0, 'big': 0}
+        # ---- outputs: one allocation per pool, one view per output the caller sees (as_strided: slice + view would be two ops)
+        pools = [torch.empty((unit * n,), dtype=torch.float32, device=dev) for unit in lay.pool_unit_floats]
 
-        def carve(pool, name, shape):
-            buf = small if pool == 'small' else big
-            size = 1
-            for d in shape:
-                size *= d
-            t = buf.as_strided(shape, _row_major_strides(shape), pos[pool])     # one view op (slice + view would be two)
-            pos[pool] += size
-            return t
+        def view(slot):
+            pool, offset, dims, strides = slot
+            return pools[pool].as_strided((n,) + dims, strides, n * offset)
 
         o = self.c_out
-        z_coarse = carve('big', 'z', (n, self.num_coarse))
-        o.depths_coarse = z_coarse.data_ptr()
-        z_fine = None
-        if self.num_fine:
-            z_fine = fine_in if override is not None else carve('big', 'z', (n, self.num_coarse + self.num_fine))
-            o.depths_fine = 0 if override is not None else z_fine.data_ptr()
-        out: Dict[int, Dict[str, Tensor]] = {}
-        for l in range(_lib.RENDER_LEVELS):
-            lo = o.level[l]
-            if l not in self.levels:
-                for f in _lib.LEVEL_OUT_FIELDS:
-                    setattr(lo, f, 0)
-                continue
-            s = self.samples(l)
-            d = out[l] = {}
-            for name, width in per_ray:
-                d[name] = carve('small', name, (n, 3) if width == 3 else (n,))
-                setattr(lo, name, d[name].data_ptr())
-            if not self.ndc:
-                lo.depth_ndc = lo.depth_var_ndc = 0
-            for name in ('alpha', 'visibility', 'weights'):
-                if name in self.per_sample:
-                    d[name] = carve('big', name, (n, s))
-                    setattr(lo, name, d[name].data_ptr())
-                else:
-                    setattr(lo, name, 0)
-            d['sigma'], d['raw_rgb'] = carve('big', 'sigma', (n, s, 1)), carve('big', 'raw_rgb', (n, s, 3))
-            lo.sigma, lo.raw_rgb = d['sigma'].data_ptr(), d['raw_rgb'].data_ptr()
-            lo.raw_visibility = lo.raw_visibility2 = lo.visibility2 = lo.view_dirs2 = 0
-            if self.mlps[l].desc.predict_visibility:
-                d['raw_visibility'] = carve('big', 'raw_visibility', (n, s, 1))
-                lo.raw_visibility = d['raw_visibility'].data_ptr()
-                if k_other:
-                    d['raw_visibility2'] = carve('big', 'raw_visibility2', (n, s, k_other, 1))
-                    d['visibility2'] = carve('small', 'visibility2', (n, k_other))
-                    dirs2 = carve('big', 'view_dirs2', (n, s, k_other, 3))
-                    lo.raw_visibility2, lo.visibility2, lo.view_dirs2 = d['raw_visibility2'].data_ptr(), d['visibility2'].data_ptr(), dirs2.data_ptr()
-                    if not lo.weights:      # visibility2 is composited with the level's weights
-                        lo.weights = carve('big', 'weights', (n, s)).data_ptr()
-            if self.keep:
-                d['saved'] = torch.empty((lib.snerf_mlp_saved_floats(ctypes.byref(self.mlps[l].desc), n, s),), dtype=torch.float32, device=dev)
-                lo.saved_acts = d['saved'].data_ptr()
-            else:
-                lo.saved_acts = 0
+        _lib.check(lib.snerf_render_layout_bind(ctypes.byref(lay.c), n, _ptr(pools[0]), _ptr(pools[1]), ctypes.byref(o)),
+                   'snerf_render_layout_bind')
+        z_coarse = view(lay.depths_coarse)
+        z_fine = fine_in if lay.depths_fine is None else view(lay.depths_fine)
+        out: Dict[int, Dict[str, Tensor]] = {l: {} for l in self.levels}
+        for l, name, slot in lay.returned:
+            out[l][name] = view(slot)
+        saved = [torch.empty((lib.snerf_mlp_saved_floats(ctypes.byref(self.mlps[l].desc), n, samples[l]),), dtype=torch.float32,
+                             device=dev) for l in self.levels] if self.keep else []
+        for l, t in zip(self.levels, saved):
+            o.level[l].saved_acts = t.data_ptr()
         work = None
-        if self.num_fine and override is None and 'weights' not in self.per_sample:
+        if lay.needs_workspace:
             work = torch.empty((lib.snerf_render_workspace_floats(ctypes.byref(self.cfg), n),), dtype=torch.float32, device=dev)
         if n > 0:
             with torch.cuda.device(dev):
@@ -441,7 +426,7 @@ class RenderCall:
         # what backward() needs alive is the memory behind the pointers in the structs: the two pools, the saved
         # activations and the inputs.  The output VIEWS are not kept here: under autograd they carry the node that owns
         # this object, and holding them would close a reference cycle that only the cycle collector frees (GBs per call)
-        held += [small, big] + [d['saved'] for d in out.values() if 'saved' in d]
+        held += pools + saved
         return z_coarse, z_fine, out
 
     def backward(self, grads: Dict[int, Dict[str, Optional[Tensor]]], param_grads: Dict[int, List[Tensor]],
@@ -458,7 +443,7 @@ class RenderCall:
             g = grads.get(l) or {}
             if l not in param_grads or not any(g.get(k) is not None for k in ('rgb', 'acc', 'depth', 'depth_ndc', 'sigma', 'raw_rgb')):
                 continue
-            s = self.samples(l)
+            s = self.layout.samples[l]
             cg = c_grads[l]
             for name, shape in (('rgb', (n, 3)), ('acc', (n,)), ('depth', (n,)), ('depth_ndc', (n,)), ('sigma', (n, s, 1)),
                                 ('raw_rgb', (n, s, 3))):

@@ -1,0 +1,206 @@
+// simplenerf_amd/csrc/render_layout.h on the host (no GPU; built with AddressSanitizer + UBSan by tests/test_render_layout_host.py):
+// over the product of the options that shape a render call's outputs, the slots of each pool tile it exactly, presence and
+// `returned` follow the rules written out below, the bound pointers stay inside the pools; and two layouts derived by hand from the
+// carve order are pinned number by number.
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../../simplenerf_amd/csrc/render_layout.h"
+
+using namespace snerf::renderlayout;
+
+#define CHECK(cond)                                                                                         \
+    do {                                                                                                    \
+        if (!(cond)) { std::printf("check failed at %s:%d: %s\n", __FILE__, __LINE__, #cond); return 1; }   \
+    } while (0)
+
+static long long unit_of(const snerf_render_slot& s) {
+    long long unit = 1;
+    for (int i = 0; i < s.rank; ++i) unit *= s.dims[i];
+    return unit;
+}
+
+static bool shape_is(const snerf_render_slot& s, std::vector<int> dims) {
+    return s.rank == (int)dims.size() && std::equal(dims.begin(), dims.end(), s.dims);
+}
+
+struct Case {
+    std::vector<int> levels;
+    int ndc, mask, vis_levels, num_other, fine_given, keep, num_coarse, num_fine;   // vis_levels: 0 none, 1 level 0, 2 levels 0 and 3
+};
+
+static int check_case(const Case& t) {
+    snerf_render_config cfg{};
+    cfg.ndc = t.ndc; cfg.num_coarse = t.num_coarse; cfg.num_fine = t.num_fine; cfg.keep_activations = t.keep;
+    snerf_mlp_desc descs[SNERF_RENDER_LEVELS] = {};
+    snerf_render_mlp mlps[SNERF_RENDER_LEVELS] = {};
+    bool present[SNERF_RENDER_LEVELS] = {};
+    for (int l : t.levels) { present[l] = true; mlps[l].desc = &descs[l]; }
+    if (t.vis_levels >= 1) descs[0].predict_visibility = 1;
+    if (t.vis_levels >= 2) descs[3].predict_visibility = 1;
+    snerf_render_layout lay;
+    std::memset(&lay, 0xAB, sizeof(lay));        // the query leaves nothing of this behind
+    CHECK(query(&cfg, mlps, t.num_other, t.mask, t.fine_given != 0, &lay) == nullptr);
+
+    const bool fine = present[3];
+    const int k = t.num_other;
+    CHECK(lay.num_fine == (fine ? t.num_fine : 0));
+    for (int l = 0; l < SNERF_RENDER_LEVELS; ++l) CHECK(lay.samples[l] == (l < 3 ? t.num_coarse : t.num_coarse + (fine ? t.num_fine : 0)));
+    CHECK(lay.needs_workspace == (fine && !t.fine_given && !(t.mask & 4)));
+    CHECK(lay.depths_coarse.present && lay.depths_coarse.returned && shape_is(lay.depths_coarse, {t.num_coarse}));
+    CHECK((lay.depths_fine.present != 0) == (fine && !t.fine_given));
+    if (lay.depths_fine.present) CHECK(lay.depths_fine.returned && shape_is(lay.depths_fine, {t.num_coarse + t.num_fine}));
+
+    std::vector<const snerf_render_slot*> pooled[2] = {{}, {&lay.depths_coarse}};
+    if (lay.depths_fine.present) pooled[1].push_back(&lay.depths_fine);
+    CHECK(lay.depths_coarse.pool == SNERF_POOL_PER_SAMPLE && (!lay.depths_fine.present || lay.depths_fine.pool == SNERF_POOL_PER_SAMPLE));
+    for (int l = 0; l < SNERF_RENDER_LEVELS; ++l) {
+        const snerf_render_slot* f = lay.level[l];
+        const int s = lay.samples[l];
+        const bool vis = present[l] && descs[l].predict_visibility, vis2 = vis && k > 0;
+        const bool want_weights = (t.mask & 4) != 0, hidden_weights = vis2 && !want_weights;
+        // presence, field by field
+        const bool expected[SNERF_RENDER_FIELDS] = {
+            present[l], present[l], present[l], present[l],                                       // rgb, acc, depth, depth_var
+            present[l] && t.ndc, present[l] && t.ndc,                                             // depth_ndc, depth_var_ndc
+            present[l] && (t.mask & 1), present[l] && (t.mask & 2), present[l] && (want_weights || hidden_weights),
+            present[l], present[l],                                                               // sigma, raw_rgb
+            present[l] && t.keep,                                                                 // saved_acts
+            vis, vis2, vis2, vis2};                                                               // raw_visibility, raw_visibility2, visibility2, view_dirs2
+        for (int i = 0; i < SNERF_RENDER_FIELDS; ++i) {
+            CHECK((f[i].present != 0) == expected[i]);
+            if (!f[i].present) { CHECK(!f[i].returned && f[i].rank == 0 && f[i].unit_offset == 0); continue; }
+            const bool scratch = i == SNERF_FIELD_VIEW_DIRS2 || i == SNERF_FIELD_SAVED_ACTS || (i == SNERF_FIELD_WEIGHTS && !want_weights);
+            CHECK((f[i].returned != 0) == !scratch);
+            const bool per_ray = i <= SNERF_FIELD_DEPTH_VAR_NDC || i == SNERF_FIELD_VISIBILITY2;
+            CHECK(f[i].pool == (i == SNERF_FIELD_SAVED_ACTS ? SNERF_POOL_OWN : per_ray ? SNERF_POOL_PER_RAY : SNERF_POOL_PER_SAMPLE));
+            if (f[i].pool != SNERF_POOL_OWN) pooled[f[i].pool].push_back(&f[i]);
+        }
+        if (!present[l]) continue;
+        CHECK(shape_is(f[SNERF_FIELD_RGB], {3}) && shape_is(f[SNERF_FIELD_ACC], {}) && shape_is(f[SNERF_FIELD_DEPTH], {}) &&
+              shape_is(f[SNERF_FIELD_DEPTH_VAR], {}) && shape_is(f[SNERF_FIELD_SIGMA], {s, 1}) && shape_is(f[SNERF_FIELD_RAW_RGB], {s, 3}));
+        if (t.ndc) CHECK(shape_is(f[SNERF_FIELD_DEPTH_NDC], {}) && shape_is(f[SNERF_FIELD_DEPTH_VAR_NDC], {}));
+        for (int i : {SNERF_FIELD_ALPHA, SNERF_FIELD_VISIBILITY, SNERF_FIELD_WEIGHTS})
+            if (f[i].present) CHECK(shape_is(f[i], {s}));
+        if (vis) CHECK(shape_is(f[SNERF_FIELD_RAW_VISIBILITY], {s, 1}));
+        if (vis2) CHECK(shape_is(f[SNERF_FIELD_RAW_VISIBILITY2], {s, k, 1}) && shape_is(f[SNERF_FIELD_VISIBILITY2], {k}) &&
+                        shape_is(f[SNERF_FIELD_VIEW_DIRS2], {s, k, 3}));
+        if (f[SNERF_FIELD_SAVED_ACTS].present) CHECK(shape_is(f[SNERF_FIELD_SAVED_ACTS], {}));
+    }
+    // the slots of each pool tile it: sorted by offset, each begins where the one before ends, from 0 to the pool's size
+    for (int p = 0; p < 2; ++p) {
+        std::sort(pooled[p].begin(), pooled[p].end(), [](const snerf_render_slot* a, const snerf_render_slot* b) { return a->unit_offset < b->unit_offset; });
+        long long at = 0;
+        for (const snerf_render_slot* s : pooled[p]) {
+            CHECK(s->unit_offset == at);
+            at += unit_of(*s);
+        }
+        CHECK(at == lay.pool_unit_floats[p]);
+    }
+    // bound to real pools, every output can be written over its whole extent (AddressSanitizer watches the ends)
+    const long long n = 3;
+    std::vector<float> ray_pool(n * lay.pool_unit_floats[0]), sample_pool(n * lay.pool_unit_floats[1]);
+    snerf_render_outputs out;
+    std::memset(&out, 0xCD, sizeof(out));
+    bind(&lay, n, ray_pool.data(), sample_pool.data(), &out);
+    CHECK(out.depths_coarse == sample_pool.data());
+    CHECK((out.depths_fine != nullptr) == (lay.depths_fine.present != 0));
+    for (int l = 0; l < SNERF_RENDER_LEVELS; ++l)
+        for (int i = 0; i < SNERF_RENDER_FIELDS; ++i) {
+            const snerf_render_slot& s = lay.level[l][i];
+            float* p = out.level[l].*kField[i];
+            CHECK((p != nullptr) == (s.present && s.pool != SNERF_POOL_OWN));
+            if (p) std::fill(p, p + n * unit_of(s), 1.f);
+        }
+    if (present[0]) CHECK(out.level[0].rgb == ray_pool.data());
+    return 0;
+}
+
+static int check_sweep() {
+    const std::vector<std::vector<int>> level_sets = {{0}, {0, 3}, {0, 1, 2}, {0, 1, 2, 3}, {0, 1, 2, 3, 4, 5}};
+    long long cases = 0;
+    for (const auto& levels : level_sets)
+        for (int ndc = 0; ndc < 2; ++ndc)
+            for (int mask = 0; mask < 8; ++mask)
+                for (int vis = 0; vis < 3; ++vis)
+                    for (int k : {0, 2})
+                        for (int given = 0; given < 2; ++given)
+                            for (int keep = 0; keep < 2; ++keep)
+                                for (int counts = 0; counts < 2; ++counts) {
+                                    const Case t{levels, ndc, mask, vis, k, given, keep, counts ? 3 : 4, counts ? 5 : 4};
+                                    if (check_case(t)) {
+                                        std::printf("  levels %zu ndc %d mask %d vis %d num_other %d given %d keep %d counts %d\n", levels.size(),
+                                                    ndc, mask, vis, k, given, keep, counts);
+                                        return 1;
+                                    }
+                                    ++cases;
+                                }
+    CHECK(cases == 5 * 2 * 8 * 3 * 2 * 2 * 2 * 2);
+    return 0;
+}
+
+// Two layouts worked out by hand from the carve order of the bindings before the layout had an owner.
+static int check_pinned() {
+    snerf_mlp_desc plain{}, vis{};
+    vis.predict_visibility = 1;
+    snerf_render_layout lay;
+    {   // levels {0,3}, no NDC, alpha only, no visibility, 4 + 4 samples, fine depths not given
+        snerf_render_config cfg{};
+        cfg.num_coarse = 4; cfg.num_fine = 4;
+        snerf_render_mlp mlps[SNERF_RENDER_LEVELS] = {};
+        mlps[0].desc = mlps[3].desc = &plain;
+        CHECK(query(&cfg, mlps, 0, 1, false, &lay) == nullptr);
+        CHECK(lay.pool_unit_floats[0] == 12 && lay.pool_unit_floats[1] == 72 && lay.needs_workspace == 1);
+        const snerf_render_slot *a = lay.level[0], *b = lay.level[3];
+        CHECK(a[SNERF_FIELD_RGB].unit_offset == 0 && a[SNERF_FIELD_ACC].unit_offset == 3 && a[SNERF_FIELD_DEPTH].unit_offset == 4 &&
+              a[SNERF_FIELD_DEPTH_VAR].unit_offset == 5);
+        CHECK(b[SNERF_FIELD_RGB].unit_offset == 6 && b[SNERF_FIELD_ACC].unit_offset == 9 && b[SNERF_FIELD_DEPTH].unit_offset == 10 &&
+              b[SNERF_FIELD_DEPTH_VAR].unit_offset == 11);
+        CHECK(lay.depths_coarse.unit_offset == 0 && unit_of(lay.depths_coarse) == 4 && lay.depths_fine.unit_offset == 4 && unit_of(lay.depths_fine) == 8);
+        CHECK(a[SNERF_FIELD_ALPHA].unit_offset == 12 && a[SNERF_FIELD_SIGMA].unit_offset == 16 && a[SNERF_FIELD_RAW_RGB].unit_offset == 20);
+        CHECK(b[SNERF_FIELD_ALPHA].unit_offset == 32 && b[SNERF_FIELD_SIGMA].unit_offset == 40 && b[SNERF_FIELD_RAW_RGB].unit_offset == 48);
+    }
+    {   // level {0} predicting visibility, NDC, alpha only, two secondary views, 4 coarse samples, no fine pass
+        snerf_render_config cfg{};
+        cfg.ndc = 1; cfg.num_coarse = 4;
+        snerf_render_mlp mlps[SNERF_RENDER_LEVELS] = {};
+        mlps[0].desc = &vis;
+        CHECK(query(&cfg, mlps, 2, 1, false, &lay) == nullptr);
+        CHECK(lay.pool_unit_floats[0] == 10 && lay.pool_unit_floats[1] == 64 && lay.needs_workspace == 0);
+        const snerf_render_slot* a = lay.level[0];
+        CHECK(a[SNERF_FIELD_RGB].unit_offset == 0 && a[SNERF_FIELD_ACC].unit_offset == 3 && a[SNERF_FIELD_DEPTH].unit_offset == 4 &&
+              a[SNERF_FIELD_DEPTH_VAR].unit_offset == 5 && a[SNERF_FIELD_DEPTH_NDC].unit_offset == 6 &&
+              a[SNERF_FIELD_DEPTH_VAR_NDC].unit_offset == 7 && a[SNERF_FIELD_VISIBILITY2].unit_offset == 8 && unit_of(a[SNERF_FIELD_VISIBILITY2]) == 2);
+        CHECK(lay.depths_coarse.unit_offset == 0 && !lay.depths_fine.present);
+        CHECK(a[SNERF_FIELD_ALPHA].unit_offset == 4 && a[SNERF_FIELD_SIGMA].unit_offset == 8 && a[SNERF_FIELD_RAW_RGB].unit_offset == 12 &&
+              a[SNERF_FIELD_RAW_VISIBILITY].unit_offset == 24 && a[SNERF_FIELD_RAW_VISIBILITY2].unit_offset == 28 &&
+              unit_of(a[SNERF_FIELD_RAW_VISIBILITY2]) == 8 && a[SNERF_FIELD_VIEW_DIRS2].unit_offset == 36 &&
+              unit_of(a[SNERF_FIELD_VIEW_DIRS2]) == 24 && a[SNERF_FIELD_WEIGHTS].unit_offset == 60 && unit_of(a[SNERF_FIELD_WEIGHTS]) == 4 &&
+              !a[SNERF_FIELD_WEIGHTS].returned);
+    }
+    return 0;
+}
+
+static int check_refusals() {
+    snerf_mlp_desc plain{};
+    snerf_render_config cfg{};
+    cfg.num_coarse = 4;
+    snerf_render_mlp mlps[SNERF_RENDER_LEVELS] = {};
+    snerf_render_layout lay;
+    CHECK(query(&cfg, mlps, 0, 1, false, &lay) != nullptr);            // no main coarse level
+    mlps[0].desc = &plain;
+    CHECK(query(&cfg, mlps, 0, 1, false, nullptr) != nullptr);
+    CHECK(query(nullptr, mlps, 0, 1, false, &lay) != nullptr && query(&cfg, nullptr, 0, 1, false, &lay) != nullptr);
+    CHECK(query(&cfg, mlps, -1, 1, false, &lay) != nullptr && query(&cfg, mlps, 0, 8, false, &lay) != nullptr);
+    cfg.num_coarse = 0;
+    CHECK(query(&cfg, mlps, 0, 1, false, &lay) != nullptr);
+    return 0;
+}
+
+int main() {
+    if (check_sweep() || check_pinned() || check_refusals()) return 1;
+    std::printf("render_layout_test: OK\n");
+    return 0;
+}

@@ -46,6 +46,79 @@ def test_eval_outputs_are_identical(kind, precision):
             assert torch.equal(a['z_vals_fine'], z) and all(torch.equal(a[k], b[k]) for k in a)
 
 
+def test_predicted_visibility_with_secondary_views_is_identical():
+    """The route with the most layout rules -- predict_visibility levels, two secondary views (scratch view directions, weights
+    carved only for visibility2, visibility2 among the per-ray outputs), NDC, every per-sample output -- through both bindings, with
+    and without injected fine depths."""
+    from tests.test_gpu_model import build
+    from tests.test_oracle_golden import visibility_case
+    g, cfg, batch = visibility_case('ndc_eval')
+    models = {b: build(synth.with_overrides(cfg, hip_host_binding=b), g).eval() for b in ('torch_ext', 'ctypes')}
+    batch = {k: v.to(DEV) if isinstance(v, torch.Tensor) else v for k, v in batch.items()}
+    with torch.no_grad():
+        for z_fine in (None, torch.from_numpy(g['out_z_vals_fine'])):
+            for retraw in (True, False):          # (without retraw the weights are carved but not returned)
+                if z_fine is not None:
+                    for m in models.values():
+                        m.set_random_draws({'z_vals_fine': z_fine})
+                a, b = (models[name](batch, retraw=retraw, sec_views_vis=True) for name in ('torch_ext', 'ctypes'))
+                assert list(a.keys()) == list(b.keys()) and ('weights_fine' in a) == retraw
+                assert {'visibility2_coarse', 'visibility2_fine'} <= set(a) and (not retraw or 'raw_visibility2_fine' in a)
+                for k in a:
+                    assert a[k].shape == b[k].shape and torch.equal(a[k], b[k]), (k, retraw, z_fine is not None)
+                if z_fine is not None and retraw:
+                    assert torch.equal(a['z_vals_fine'].cpu(), z_fine)
+
+
+# config 3 in training mode (levels 0-3, NDC, 64 + 128 samples, every per-sample output): floats per ray from the start of its pool
+# of every output, worked out by hand from the order the pools are carved in -- per level rgb, acc, depth, depth_var, depth_ndc,
+# depth_var_ndc in the per-ray pool; z_vals_coarse, z_vals_fine, then per level alpha, visibility, weights, sigma, raw_rgb
+CONFIG3_PER_RAY = {'rgb': 0, 'acc': 3, 'depth': 4, 'depth_var': 5, 'depth_ndc': 6, 'depth_var_ndc': 7}         # + 8 per level
+CONFIG3_PER_SAMPLE = {
+    'z_vals_coarse': 0, 'z_vals_fine': 64,
+    'alpha_coarse': 256, 'visibility_coarse': 320, 'weights_coarse': 384, 'raw_sigma_coarse': 448, 'raw_rgb_coarse': 512,
+    'points_augmentation_alpha_coarse': 704, 'points_augmentation_visibility_coarse': 768, 'points_augmentation_weights_coarse': 832,
+    'points_augmentation_raw_sigma_coarse': 896, 'points_augmentation_raw_rgb_coarse': 960,
+    'views_augmentation_alpha_coarse': 1152, 'views_augmentation_visibility_coarse': 1216, 'views_augmentation_weights_coarse': 1280,
+    'views_augmentation_raw_sigma_coarse': 1344, 'views_augmentation_raw_rgb_coarse': 1408,
+    'alpha_fine': 1600, 'visibility_fine': 1792, 'weights_fine': 1984, 'raw_sigma_fine': 2176, 'raw_rgb_fine': 2368}
+
+
+@pytest.mark.parametrize('binding', ['torch_ext', 'ctypes'])
+def test_outputs_lie_where_the_pools_were_always_carved(binding):
+    """The memory layout inside the two pools: every output of a training-mode config 3 call starts n x (the hand-derived offset)
+    floats into its pool, z_vals_coarse at the base of the per-sample pool and rgb_coarse at the base of the per-ray pool."""
+    n = 37
+    model = make('config3', binding).train()
+    batch = harness.frame_batch(synth.camera('fern', 0), True, DEV, 250000, n)
+    batch['iter_num'] = 0
+    out = model(batch)
+    expected = dict(CONFIG3_PER_SAMPLE)
+    levels = ('{}_coarse', 'points_augmentation_{}_coarse', 'views_augmentation_{}_coarse', '{}_fine')
+    per_ray = [pattern.format(k) for pattern in levels for k in CONFIG3_PER_RAY]
+    expected.update({pattern.format(k): 8 * l + at for l, pattern in enumerate(levels) for k, at in CONFIG3_PER_RAY.items()})
+    views = {k: v for k, v in out.items() if 'rgb_view_' not in k}                 # (those name raw_rgb a second time)
+    assert set(views) == set(expected), set(views) ^ set(expected)
+    for k, v in views.items():
+        assert v.is_contiguous() and v.storage_offset() == n * expected[k], (k, v.storage_offset(), n * expected[k])
+        pool = out['rgb_coarse'] if k in per_ray else out['z_vals_coarse']
+        assert v.untyped_storage().data_ptr() == pool.untyped_storage().data_ptr(), k
+    assert out['z_vals_coarse'].data_ptr() == out['z_vals_coarse'].untyped_storage().data_ptr()
+    assert out['rgb_coarse'].data_ptr() == out['rgb_coarse'].untyped_storage().data_ptr()
+    assert out['z_vals_coarse'].untyped_storage().nbytes() == 4 * n * 2944 and out['rgb_coarse'].untyped_storage().nbytes() == 4 * n * 32
+
+
+@pytest.mark.parametrize('binding', ['torch_ext', 'ctypes'])
+def test_a_call_without_rays_returns_empty_outputs_of_the_right_shapes(binding):
+    model = make('config2', binding).eval()
+    cam = synth.camera('fern', 0)
+    with torch.no_grad():
+        full, out = (model(harness.frame_batch(cam, True, DEV, 1000, n), retraw=True) for n in (4, 0))
+    assert list(out.keys()) == list(full.keys())
+    for k in out:
+        assert tuple(out[k].shape) == (0,) + tuple(full[k].shape[1:]), k
+
+
 @pytest.mark.parametrize('precision', ['fp32', 'f16'])
 def test_training_outputs_and_gradients_are_identical(precision):
     """config 3 (four MLPs, device draws keyed by iteration and row): two backward passes (overwrite, then accumulate into the

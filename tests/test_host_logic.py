@@ -52,6 +52,58 @@ def test_descriptor_queries_need_no_gpu():
     assert lib.snerf_mlp_num_params(ctypes.byref(bad)) == 0 and b'predict_visibility' in lib.snerf_last_error()
 
 
+def test_render_layout_query_needs_no_gpu():
+    """snerf_render_layout_query through the library: the two layouts derived by hand from the bindings' carve order (the same
+    numbers as tests/native/render_layout_test.cpp), and its refusals."""
+    lib = _lib.load()
+    fields = {name: f for f, name in enumerate(_lib.LEVEL_OUT_FIELDS)}
+
+    def query(levels, num_other, mask, given, **cfg):
+        descs = {l: _lib.MlpDesc(predict_visibility=int(vis)) for l, vis in levels.items()}
+        mlps = (_lib.RenderMlp * _lib.RENDER_LEVELS)()
+        for l, d in descs.items():
+            mlps[l].desc = ctypes.pointer(d)
+        lay = _lib.RenderLayout()
+        status = lib.snerf_render_layout_query(ctypes.byref(_lib.RenderConfig(**cfg)), mlps, num_other, mask, given, ctypes.byref(lay))
+        return status, lay
+
+    def offsets(lay, level, names):
+        return [int(lay.level[level][fields[name]].unit_offset) for name in names]
+
+    def unit(slot):
+        return int(numpy.prod(slot.dims[:slot.rank], dtype=numpy.int64))
+
+    # levels {0,3}, no NDC, alpha only, 4 + 4 samples, fine depths not given
+    status, lay = query({0: False, 3: False}, 0, 1, 0, num_coarse=4, num_fine=4)
+    assert status == 0 and list(lay.pool_unit_floats) == [12, 72] and lay.needs_workspace == 1
+    assert list(lay.samples) == [4, 4, 4, 8, 8, 8] and lay.num_fine == 4
+    assert offsets(lay, 0, ('rgb', 'acc', 'depth', 'depth_var')) == [0, 3, 4, 5]
+    assert offsets(lay, 3, ('rgb', 'acc', 'depth', 'depth_var')) == [6, 9, 10, 11]
+    assert (lay.depths_coarse.unit_offset, unit(lay.depths_coarse), lay.depths_fine.unit_offset, unit(lay.depths_fine)) == (0, 4, 4, 8)
+    assert offsets(lay, 0, ('alpha', 'sigma', 'raw_rgb')) == [12, 16, 20] and offsets(lay, 3, ('alpha', 'sigma', 'raw_rgb')) == [32, 40, 48]
+    returned = [name for name in _lib.LEVEL_OUT_FIELDS if lay.level[3][fields[name]].returned]
+    assert returned == ['rgb', 'acc', 'depth', 'depth_var', 'alpha', 'sigma', 'raw_rgb'] and not any(s.present for s in lay.level[1])
+    # level {0} predicting visibility, NDC, alpha only, two secondary views, 4 coarse samples, no fine pass
+    status, lay = query({0: True}, 2, 1, 0, ndc=1, num_coarse=4)
+    assert status == 0 and list(lay.pool_unit_floats) == [10, 64] and lay.needs_workspace == 0 and not lay.depths_fine.present
+    assert offsets(lay, 0, ('rgb', 'acc', 'depth', 'depth_var', 'depth_ndc', 'depth_var_ndc', 'visibility2')) == [0, 3, 4, 5, 6, 7, 8]
+    names = ('alpha', 'sigma', 'raw_rgb', 'raw_visibility', 'raw_visibility2', 'view_dirs2', 'weights')
+    assert lay.depths_coarse.unit_offset == 0 and offsets(lay, 0, names) == [4, 8, 12, 24, 28, 36, 60]
+    slots = lay.level[0]
+    assert [unit(slots[fields[k]]) for k in ('visibility2', 'raw_visibility2', 'view_dirs2', 'weights')] == [2, 8, 24, 4]
+    assert [name for name in _lib.LEVEL_OUT_FIELDS if slots[fields[name]].present and not slots[fields[name]].returned] == ['weights', 'view_dirs2']
+    assert tuple(slots[fields['raw_visibility2']].dims[:slots[fields['raw_visibility2']].rank]) == (4, 2, 1)
+    # refusals: a status and a message, no device
+    mlps = (_lib.RenderMlp * _lib.RENDER_LEVELS)()
+    d = _lib.MlpDesc()
+    mlps[0].desc = ctypes.pointer(d)
+    cfg = _lib.RenderConfig(num_coarse=4)
+    assert lib.snerf_render_layout_query(ctypes.byref(cfg), mlps, 0, 1, 0, None) == -1 and b'NULL' in lib.snerf_last_error()
+    status, _ = query({3: False}, 0, 1, 0, num_coarse=4, num_fine=4)
+    assert status == -1 and b'main coarse MLP is required' in lib.snerf_last_error()
+    assert lib.snerf_render_layout_bind(None, 4, None, None, None) == -1 and b'render_layout_bind' in lib.snerf_last_error()
+
+
 def test_invalid_arguments_return_errors_without_touching_the_gpu():
     lib = _lib.load()
     st = lib.snerf_coarse_depths(None, None, 4, 8, 0, None, None, None)

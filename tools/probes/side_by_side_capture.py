@@ -60,7 +60,7 @@ for i in range(repeats):
         ref_work, ref_grads = work.clone(), grads
         regions, at = {}, 0
         for l in sorted(call.levels):
-            s = call.samples(l)
+            s = call.layout.samples[l]
             inner = call.mlps[l].backward_workspace_floats(call.n, s)
             regions[l] = (at, call.n * s, inner)
             at += 4 * call.n * s + (inner + 63) // 64 * 64
