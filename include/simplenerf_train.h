@@ -152,6 +152,51 @@ int snerf_gather_dense_depth(const long long* indices, long long num_rays, long 
                              float* values_weights, float* values_ndc, snerf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * S1-S3  the scene tables from the loader's raw data (ABI 10).  Replaces the per-pixel parts of DataPreprocessor's start-up work
+ * (src/data_preprocessors/DataPreprocessor01.py), which the reference does in numpy on the host: what snerf_assemble_batch and
+ * snerf_gather_dense_depth read is built where they read it.  Every call enqueues only, allocates and synchronises nothing, uses
+ * integer atomics only (no result depends on scheduling) and keeps the reference's fp32 / fp64 operation order: the tables are
+ * bit-identical to numpy's.
+ *
+ * S1  snerf_scene_images: preprocess_images (:929-935).
+ *   images  device (num_pixels, channels) uint8, channels 3 or 4     out  device (num_pixels, 3) = (float)u8 / 255.0f
+ *   white_bkgd != 0: rgb * a + (1.0f - a) as a separate multiply and add, a = the LAST channel / 255.0f (the alpha of RGBA)
+ */
+int snerf_scene_images(const unsigned char* images, long long num_pixels, int channels, int white_bkgd, float* out,
+                       snerf_stream_t stream);
+
+/* S2  snerf_rasterise_sparse_depth: preprocess_raw_sparse_depth_data (:163-185) and, with depths_ndc, the NDC table of
+ * preprocess_sparse_depth_data (:448-452).
+ *   x, y, depth, reprojection_error  device (num_points) fp64 (pandas' dtype), the points of all views concatenated
+ *   view    device (num_points) int32, the view of each point.  A call that only enqueues cannot read it: a point whose view lies
+ *           outside [0, num_views), or whose x or y is NaN, has no pixel and is dropped by the kernel; a caller that cannot vouch
+ *           for its array checks it on the host before the upload (ops.rasterise_sparse_depth does).
+ *   pixel of a point: column clip(rint(x / divisor), 0, width-1), row clip(rint(y / divisor), 0, height-1); rint is fp64
+ *           round-half-to-even (numpy.round) and the clip comes before the integer conversion.  Of several points on one pixel
+ *           the LAST in input order wins (numpy's fancy assignment): pass 1 takes the integer maximum of the point index per
+ *           pixel, pass 2 writes one pixel per thread.
+ *   depths, errors  device (num_views*height*width): (float)(depth * scale) and (float)reprojection_error of the winner, -1 where
+ *           a pixel has no point (num_points == 0: everywhere)
+ *   depths_ndc      device (same) or NULL: snerf_depth_table_to_ndc of `depths` with `near` (the reference passes 1, :450), by the
+ *           same launch; needs camera_table (snerf_camera_table), which may be NULL otherwise
+ *   workspace       device, snerf_rasterise_sparse_depth_workspace_bytes(...) bytes (the int32 winner table; initialised here)
+ *   At most 2^31-1 points.
+ */
+long long snerf_rasterise_sparse_depth_workspace_bytes(int num_views, int height, int width);
+int snerf_rasterise_sparse_depth(const double* x, const double* y, const double* depth, const double* reprojection_error,
+                                 const int* view, long long num_points, double scale, double divisor, const float* camera_table,
+                                 float near, int num_views, int height, int width, float* depths, float* errors, float* depths_ndc,
+                                 void* workspace, snerf_stream_t stream);
+
+/* S3  snerf_depth_table_to_ndc: convert_depth_to_ndc (:455-463) over a per-pixel table, as :448-452 (near = 1) and :474-478
+ * (near = the scene's) use it.  The world ray of every pixel is recomputed from its view's camera-table row (same arithmetic as
+ * K1); in fp32, in this order:  tn = -(near + oz) / dz;  oz' = oz + tn * dz;  ndc = 1 - oz' / (oz' + (depth - tn) * dz);  then -1
+ * where depth == -1.
+ *   depths, depths_ndc  device (num_views*height*width), two distinct buffers */
+int snerf_depth_table_to_ndc(const float* depths, const float* camera_table, int num_views, int height, int width, float near,
+                             float* depths_ndc, snerf_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * B2  shuffled index stream.  Replaces the host-side index list of generate_indices / select_batch_indices (:252-270,
  * :556-563: numpy.arange + numpy.random.shuffle per epoch, sliced per batch, copied to the device) by positions
  * [first, first+count) of a keyed pseudo-random PERMUTATION of the candidate set, computed on the fly (balanced

@@ -192,6 +192,12 @@ SIGNATURES = {
     'snerf_assemble_batch': (c_int, [c_void_p, c_longlong, c_longlong, _FP, c_int, c_int, c_int, _FP, _FP, _FP, _FP, c_int,
                                      c_float, c_float, c_float, c_float, c_longlong, c_longlong, POINTER(Batch), c_void_p]),
     'snerf_gather_dense_depth': (c_int, [c_void_p, c_longlong, c_longlong, c_longlong, _FP, _FP, _FP, _FP, _FP, _FP, c_void_p]),
+    # the scene tables from the loader's raw data (S1-S3)
+    'snerf_scene_images': (c_int, [c_void_p, c_longlong, c_int, c_int, _FP, c_void_p]),
+    'snerf_rasterise_sparse_depth_workspace_bytes': (c_longlong, [c_int, c_int, c_int]),
+    'snerf_rasterise_sparse_depth': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_double, c_double, _FP,
+                                             c_float, c_int, c_int, c_int, _FP, _FP, _FP, c_void_p, c_void_p]),
+    'snerf_depth_table_to_ndc': (c_int, [_FP, _FP, c_int, c_int, c_int, c_float, _FP, c_void_p]),
     'snerf_shuffled_indices': (c_int, [c_ulonglong, c_ulonglong, c_longlong, c_longlong, c_longlong, c_void_p, c_int,
                                        c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'snerf_random_uniform': (c_int, [c_ulonglong, c_uint, c_longlong, c_void_p, c_longlong, c_int, _FP, c_void_p]),

@@ -25,7 +25,9 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=o
 # SLP vectoriser: it packs neighbouring scalar fp32 operations into v_pk_*_f32 and, when a shared factor sits in the odd register
 # of a pair, selects it with op_sel:[0,1] -- the one operand selection that miscomputes beside another kernel's MFMAs on MI355X
 # (opaque_pair() in csrc/mlp_device.h; tools/probes/pk_opsel_hazard.hip).  These kernels are memory-bound: nothing to lose.
-FILE_FLAGS = {'composite': ['-fno-slp-vectorize'], 'losses': ['-fno-slp-vectorize']}
+# scene.hip runs at start-up, beside nothing, but the library is checked as a whole (hazardous_packed_forms) and its per-pixel ray
+# arithmetic vectorises into that form.
+FILE_FLAGS = {'composite': ['-fno-slp-vectorize'], 'losses': ['-fno-slp-vectorize'], 'scene': ['-fno-slp-vectorize']}
 OBJDUMP = os.environ.get('LLVM_OBJDUMP', '/opt/rocm/lib/llvm/bin/llvm-objdump')
 HAZARDOUS_PACKED_FORM = r'v_pk_\w+_f32 .*op_sel:\[0,1'     # low result <- HIGH register of the second source
 

@@ -11,8 +11,9 @@ the reference's switch (:35): each (n, 1), the pixel-ray rows gathered from the 
 ``common_data`` = {poses, intrinsics, images (each with a leading per-GPU axis of ``len(configs['device'])``, default 1),
 resolution}.
 
-``scene`` is what the reference's preprocessing leaves in ``preprocessed_data_dict`` -- dataset loading, pose
-recentring and sparse-depth rasterisation stay outside this build (out of scope):
+``scene`` is what the reference's preprocessing leaves in ``preprocessed_data_dict``; ``DataPreprocessor01.DataPreprocessor``
+builds it from the loader's raw data (pose recentring on the host, images, sparse-depth rasterisation and NDC depth tables on
+the device) and owns a BatchAssembler.  Dataset loading stays outside this build (out of scope):
     poses (V,4,4) processed camera-to-world, intrinsics (V,3,3), images (V,h,w,3) float in [0,1], resolution (h,w),
     near, far [, near_ndc, far_ndc], frame_nums (V,), and optionally the dense (V*h*w,) tables sparse_depths,
     sparse_errors, sparse_depths_ndc (<= 0 / -1 where a pixel has no sparse depth), and dense_depths,

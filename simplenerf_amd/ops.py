@@ -1266,6 +1266,108 @@ def gather_dense_depth(indices: Tensor, num_pixel_rays: int, depths: Tensor, wei
     return out
 
 
+# ---------------------------------------------------------------------------------------------- f2 scene tables (S1-S3)
+def scene_images(images: Tensor, white_bkgd: bool = False) -> Tensor:
+    """One launch: (..., C) uint8 images on the device, C = 3 or 4 -> (..., 3) float32, ``u8 / 255`` and, with ``white_bkgd``,
+    ``rgb * a + (1 - a)`` over the last channel (the reference's preprocess_images)."""
+    lib = _lib.load()
+    images = _typed(images, 'images', (torch.uint8,))
+    if images.dim() < 2 or images.shape[-1] not in (3, 4):
+        raise RuntimeError(f'images: expected (..., 3) or (..., 4), got {tuple(images.shape)}')
+    channels = int(images.shape[-1])
+    out = torch.empty(tuple(images.shape[:-1]) + (3,), dtype=torch.float32, device=images.device)
+    pixels = images.numel() // channels
+    if pixels == 0:
+        return out
+    with torch.cuda.device(images.device):
+        st = lib.snerf_scene_images(_ptr(images), pixels, channels, int(bool(white_bkgd)), _ptr(out), _stream())
+    _lib.check(st, 'snerf_scene_images')
+    return out
+
+
+MAX_SPARSE_POINTS = 2 ** 31 - 1      # the winner table of the rasteriser holds int32 point indices
+
+
+def _points(device, x, y, depth, error, view, num_views: int):
+    """The five point arrays of the rasteriser as device tensors.  Host arrays (numpy / CPU tensors: what a loader hands over)
+    are checked here -- finite coordinates, views inside [0, num_views) -- and uploaded; device tensors are taken as they are
+    (reading them back would be a host round trip: the kernel drops a point without a pixel)."""
+    fields = {'x': x, 'y': y, 'depth': depth, 'reprojection_error': error}
+    on_device = [isinstance(a, torch.Tensor) and a.is_cuda for a in (*fields.values(), view)]
+    if all(on_device):
+        out = [_typed(a, name, (torch.float64,)).reshape(-1) for name, a in fields.items()]
+        out.append(_typed(view, 'view', (torch.int32,)).reshape(-1))
+    elif any(on_device):
+        raise RuntimeError('rasterise_sparse_depth: pass the point arrays either all on the host or all on the GPU')
+    else:
+        host = {name: numpy.ascontiguousarray(numpy.asarray(a, dtype=numpy.float64)).reshape(-1) for name, a in fields.items()}
+        views = numpy.asarray(view).reshape(-1)
+        for name in ('x', 'y'):
+            if not numpy.isfinite(host[name]).all():
+                raise ValueError(f'rasterise_sparse_depth: {name} has non-finite coordinates (the reference casts them to an '
+                                 f'undefined integer)')
+        if views.size and (views.min() < 0 or views.max() >= num_views):
+            raise RuntimeError(f'rasterise_sparse_depth: view numbers span [{views.min()}, {views.max()}], outside [0, {num_views})')
+        out = [torch.from_numpy(a).to(device) for a in host.values()]
+        out.append(torch.from_numpy(numpy.ascontiguousarray(views.astype(numpy.int32))).to(device))
+    count = out[0].shape[0]
+    if any(t.shape[0] != count for t in out):
+        raise RuntimeError(f'rasterise_sparse_depth: point arrays of different lengths {[t.shape[0] for t in out]}')
+    if count > MAX_SPARSE_POINTS:
+        raise RuntimeError(f'rasterise_sparse_depth: {count} points, at most {MAX_SPARSE_POINTS}')
+    return out, count
+
+
+def rasterise_sparse_depth(x, y, depth, reprojection_error, view, num_views: int, resolution, scale: float = 1.0,
+                           divisor: float = 1.0, table: Optional[Tensor] = None, near: float = 1.0, device=None) -> Dict[str, Tensor]:
+    """The reference's sparse-depth tables, flat (num_views*h*w,) float32 on the device: ``depths`` = depth * scale and ``errors``
+    at the pixel ``(clip(rint(y / divisor)), clip(rint(x / divisor)))`` of each point's view, the last point in input order where
+    several share a pixel, -1 where there is none; with a camera ``table`` also ``depths_ndc`` (near plane ``near``).  Point arrays:
+    float64 ``x``, ``y``, ``depth``, ``reprojection_error`` and int32 ``view``, all views concatenated, on the host (checked and
+    uploaded) or on the GPU.  Two launches and one fill; deterministic."""
+    lib = _lib.load()
+    h, w, v = int(resolution[0]), int(resolution[1]), int(num_views)
+    if v < 1 or h < 1 or w < 1:
+        raise RuntimeError(f'rasterise_sparse_depth: bad sizes ({v} views, {h}x{w})')
+    if table is not None:
+        table = _dev(table, 'camera table', (v, _lib.CAMERA_FLOATS))
+        device = table.device
+    elif isinstance(x, torch.Tensor) and x.is_cuda:
+        device = x.device
+    if device is None:
+        raise RuntimeError('rasterise_sparse_depth: no device (pass device= with host arrays and no camera table)')
+    dev = torch.device(device)
+    (px, py, pd, pe, pv), count = _points(dev, x, y, depth, reprojection_error, view, v)
+    f = lambda: torch.empty((v * h * w,), dtype=torch.float32, device=dev)
+    out = {'depths': f(), 'errors': f()}
+    if table is not None:
+        out['depths_ndc'] = f()
+    workspace = torch.empty((int(lib.snerf_rasterise_sparse_depth_workspace_bytes(v, h, w)),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        st = lib.snerf_rasterise_sparse_depth(_ptr(px), _ptr(py), _ptr(pd), _ptr(pe), _ptr(pv), count, float(scale), float(divisor),
+                                              _ptr(table), float(near), v, h, w, _ptr(out['depths']), _ptr(out['errors']),
+                                              _ptr(out.get('depths_ndc')), _ptr(workspace), _stream())
+    _lib.check(st, 'snerf_rasterise_sparse_depth')
+    return out
+
+
+def depth_table_to_ndc(depths: Tensor, table: Tensor, resolution, near: float) -> Tensor:
+    """One launch: the reference's convert_depth_to_ndc over a per-pixel depth table (num_views*h*w entries, any shape) with the
+    rays recomputed from the camera ``table``; -1 stays -1.  Returns a tensor of the input's shape."""
+    lib = _lib.load()
+    h, w = int(resolution[0]), int(resolution[1])
+    v = table.shape[0]
+    table = _dev(table, 'camera table', (v, _lib.CAMERA_FLOATS))
+    depths = _dev(depths, 'depths')
+    if depths.numel() != v * h * w:
+        raise RuntimeError(f'depths: {depths.numel()} entries, expected {v}*{h}*{w} (one per pixel)')
+    out = torch.empty_like(depths)
+    with torch.cuda.device(depths.device):
+        st = lib.snerf_depth_table_to_ndc(_ptr(depths), _ptr(table), v, h, w, float(near), _ptr(out), _stream())
+    _lib.check(st, 'snerf_depth_table_to_ndc')
+    return out
+
+
 def shuffled_indices(seed: int, epoch: int, first: int, count: int, domain: int, device, candidates: Optional[Tensor] = None,
                      num_views: int = 0, resolution=(0, 0), crop=None, at: Optional[Tensor] = None, sparse: bool = False) -> Tensor:
     """Positions [first, first+count) of epoch ``epoch``'s permutation of the candidate pixels, as global pixel indices.

@@ -449,6 +449,43 @@ def training_scene(seed: int = 0, num_views: int = 3, height: int = 756, width: 
             'sparse_depths_ndc': numpy.where(has, 1.0 - 1.0 / numpy.maximum(depth, 1e-3), -1.0).astype(numpy.float32).reshape(-1)}
 
 
+def raw_scene(seed: int = 0, num_views: int = 3, height: int = 48, width: int = 64, points_per_view: int = 40,
+              frame_nums=None, rgba: bool = False, dense_dtype=None, missing_fraction: float = 0.02) -> dict:
+    """What a data loader of the reference hands its ``DataPreprocessor`` (``raw_data_dict``), seeded: ``frame_nums``, ``nerf_data``
+    {uint8 ``images`` (V,h,w,3 -- or 4 with a random alpha when ``rgba``), float64 world-to-camera ``extrinsics`` (V,4,4), float64
+    ``intrinsics`` (V,3,3; the focal length differs a little per view), ``bounds`` (2,), ``resolution``}, ``sparse_depth_data``
+    {frame number: {x, y, depth, reprojection_error}} with ``points_per_view`` float64 points per view (plain dicts of arrays) and,
+    with ``dense_dtype``, ``dense_depth_data`` {``depth_values``, ``depth_weights``} of that dtype, a ``missing_fraction`` at -1."""
+    scene = synth_scene(seed, num_views, height, width)
+    rng = numpy.random.RandomState(seed + 100)
+    extrinsics = numpy.zeros((num_views, 4, 4))
+    for v in range(num_views):
+        extrinsics[v, :3, :3] = _rotation(*(0.05 * rng.standard_normal(3)))
+        extrinsics[v, :3, 3] = [0.4 * rng.standard_normal(), 0.3 * rng.standard_normal(), 0.1 * rng.standard_normal()]
+        extrinsics[v, 3, 3] = 1
+    intrinsics = scene['intrinsics'].astype(numpy.float64)
+    for v in range(num_views):
+        intrinsics[v, 0, 0] *= 1 + 0.013 * v
+        intrinsics[v, 1, 1] *= 1 + 0.011 * v
+    images = numpy.round(scene['images'] * 255).astype(numpy.uint8)
+    if rgba:
+        images = numpy.concatenate([images, rng.randint(0, 256, size=images.shape[:3] + (1,)).astype(numpy.uint8)], -1)
+    frame_nums = numpy.arange(num_views) if frame_nums is None else numpy.asarray(frame_nums)
+    sparse = {int(f): {'x': rng.uniform(0, width - 1, points_per_view), 'y': rng.uniform(0, height - 1, points_per_view),
+                       'depth': rng.uniform(2.5, 6.0, points_per_view), 'reprojection_error': rng.uniform(0.1, 2.0, points_per_view)}
+              for f in frame_nums}
+    raw = {'frame_nums': frame_nums,
+           'nerf_data': {'images': images, 'extrinsics': extrinsics, 'intrinsics': intrinsics, 'bounds': numpy.array([2.0, 7.0]),
+                         'resolution': (height, width)},
+           'sparse_depth_data': sparse}
+    if dense_dtype is not None:
+        depth = scene['true_depth'].astype(numpy.float64) + 0.05 * rng.standard_normal(scene['true_depth'].shape)
+        depth[rng.uniform(size=depth.shape) < missing_fraction] = -1.0
+        raw['dense_depth_data'] = {'depth_values': depth.astype(dense_dtype),
+                                   'depth_weights': rng.uniform(0.05, 1.0, size=depth.shape).astype(dense_dtype)}
+    return raw
+
+
 def training_configs(precision: str = 'fp32', num_rays: int = 2048, num_sparse: int = 2048, seed: int = 0) -> dict:
     """The shipped LLFF experiment (src/NerfLlffTrainerTester01.py:245-440) restricted to the keys this build reads:
     config-3 model, 2048 pixel rays + 2048 sparse-depth rays per iteration in sub-batches of 2048, the nine losses,
