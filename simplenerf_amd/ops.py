@@ -14,12 +14,14 @@ from . import _lib
 from ._lib import MlpDesc
 
 Tensor = torch.Tensor
-PRECISION_FP32 = 0   # fp32 MFMA
-PRECISION_F16X3 = 1  # fp16 hi/lo split, 3 MFMAs per product, fp32 accumulate: fp32-grade results
-PRECISION_F16 = 2    # 16-bit mode: one fp16 MFMA per product, fp32 accumulate / master weights; 16-bit saved tensors
-PRECISION_BF16 = 3   # the 16-bit mode on bf16 operands (BASELINE config 5's literal dtype): no range limit, 8 significand bits
-PRECISION_F16S8 = 4  # the 16-bit (fp16) mode with the saved trunk activations as fp8 e4m3: only the weight gradients differ from 'f16'
-PRECISION_BF16S8 = 5  # the bf16 mode with the saved trunk activations as fp8 e4m3: only the weight gradients differ from 'bf16'
+C = _lib.C           # the headers' #defines and enumerators
+# enum snerf_precision (include/simplenerf_hip.h says what each mode computes in and keeps)
+PRECISION_FP32 = C.SNERF_PRECISION_FP32      # fp32 MFMA
+PRECISION_F16X3 = C.SNERF_PRECISION_F16X3    # fp16 hi/lo split, 3 MFMAs per product, fp32 accumulate: fp32-grade results
+PRECISION_F16 = C.SNERF_PRECISION_F16        # 16-bit mode: one fp16 MFMA per product, fp32 accumulate / master weights
+PRECISION_BF16 = C.SNERF_PRECISION_BF16      # the 16-bit mode on bf16 operands (BASELINE config 5's literal dtype): no range limit
+PRECISION_F16S8 = C.SNERF_PRECISION_F16S8    # 'f16' with the saved trunk activations as fp8 e4m3: only the weight gradients differ
+PRECISION_BF16S8 = C.SNERF_PRECISION_BF16S8  # 'bf16' with the saved trunk activations as fp8 e4m3: only the weight gradients differ
 PRECISIONS = {'fp32': PRECISION_FP32, 'f16x3': PRECISION_F16X3, 'f16': PRECISION_F16, 'bf16': PRECISION_BF16, 'f16s8': PRECISION_F16S8,
               'bf16s8': PRECISION_BF16S8}
 FP16_RANGE_PRECISIONS = (PRECISION_F16X3, PRECISION_F16, PRECISION_F16S8)     # the modes whose operands must stay below 65504 (Fp16RangeError)
@@ -53,6 +55,27 @@ def _ptr(t: Optional[Tensor]) -> ctypes.c_void_p:
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
 
 
+def _enqueue(name: str, dev, *args) -> None:
+    """Call the entry point ``name`` with ``args`` and torch's current stream of ``dev`` as its last argument; a failure is
+    reported under ``name``.  (The per-step callers -- ray generation, the render op, the MLP, the loss table, Adam, the draws, batch
+    assembly -- make the same three steps inline: they run ~50 times per training iteration.)"""
+    with torch.cuda.device(dev):
+        st = getattr(_lib.load(), name)(*args, _stream())
+    _lib.check(st, name)
+
+
+# device scratch of the library calls, one buffer per (kind, device), grown on demand; a kind's calls on one device are ordered by
+# the stream they are enqueued on, and every call writes its scratch before it reads it (but 'loss', which needs zeros at first)
+_workspaces: Dict[tuple, Tensor] = {}
+
+
+def _workspace(kind, dev: torch.device, need: int, zeroed: bool = False) -> Tensor:
+    ws = _workspaces.get((kind, dev))
+    if ws is None or ws.numel() < need:
+        ws = _workspaces[(kind, dev)] = (torch.zeros if zeroed else torch.empty)((need,), dtype=torch.uint8, device=dev)
+    return ws
+
+
 # ---------------------------------------------------------------------------------------------- fp16 range flag
 Fp16RangeError = _lib.Fp16RangeError
 RANGE_ACTIVATION, RANGE_WEIGHT = 1, 2
@@ -69,7 +92,7 @@ def range_status(clear: bool = False) -> int:
 
 
 # ---------------------------------------------------------------------------------------------- measurement hook
-PROFILE_MLP_FORWARD, PROFILE_MLP_BACKWARD = 0, 1
+PROFILE_MLP_FORWARD, PROFILE_MLP_BACKWARD = C.SNERF_PROFILE_MLP_FORWARD, C.SNERF_PROFILE_MLP_BACKWARD
 
 
 def profile_enable(capacity: int) -> None:
@@ -104,7 +127,6 @@ def generate_rays(resolution, intrinsic, pose, near: float, ndc: bool, device, f
                   num_rays: Optional[int] = None, pixel_offset: float = 0.0) -> Dict[str, Tensor]:
     """rays_o, rays_d, view_dirs (+ rays_o_ndc, rays_d_ndc) for pixels [first_ray, first_ray+num_rays) of a frame.
     intrinsic (3,3) and pose (4,4, processed camera-to-world) are host arrays."""
-    lib = _lib.load()
     h, w = int(resolution[0]), int(resolution[1])
     if num_rays is None:
         num_rays = h * w - first_ray
@@ -114,7 +136,8 @@ def generate_rays(resolution, intrinsic, pose, near: float, ndc: bool, device, f
            for name in (('rays_o', 'rays_d', 'view_dirs') + (('rays_o_ndc', 'rays_d_ndc') if ndc else ()))}
     if num_rays == 0:
         return out
-    with torch.cuda.device(out['rays_o'].device):
+    lib = _lib.load()
+    with torch.cuda.device(out['rays_o'].device):      # (inline, not _enqueue: once per step of a sharded render)
         st = lib.snerf_generate_rays(h, w, k.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                      p.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), float(pixel_offset), int(ndc),
                                      float(near), int(first_ray), int(num_rays), _ptr(out['rays_o']), _ptr(out['rays_d']),
@@ -127,7 +150,6 @@ def generate_rays(resolution, intrinsic, pose, near: float, ndc: bool, device, f
 # ---------------------------------------------------------------------------------------------- K2
 def coarse_depths(near: Tensor, far: Tensor, num_samples: int, lindisp: bool = False,
                   t_rand: Optional[Tensor] = None) -> Tensor:
-    lib = _lib.load()
     n = near.shape[0]
     near = _dev(near.reshape(-1), 'near', (n,))
     far = _dev(far.reshape(-1), 'far', (n,))
@@ -135,10 +157,8 @@ def coarse_depths(near: Tensor, far: Tensor, num_samples: int, lindisp: bool = F
     out = torch.empty((n, num_samples), dtype=torch.float32, device=near.device)
     if n == 0:
         return out
-    with torch.cuda.device(near.device):
-        st = lib.snerf_coarse_depths(_ptr(near), _ptr(far), n, int(num_samples), int(bool(lindisp)), _ptr(t_rand),
-                                     _ptr(out), _stream())
-    _lib.check(st, 'snerf_coarse_depths')
+    _enqueue('snerf_coarse_depths', near.device, _ptr(near), _ptr(far), n, int(num_samples), int(bool(lindisp)), _ptr(t_rand),
+             _ptr(out))
     return out
 
 
@@ -182,15 +202,17 @@ class PackedMlp:
         arr = (ctypes.c_void_p * len(held))(*[p.data_ptr() for p in held])
         with torch.cuda.device(self.buffer.device):
             if precision is None:
+                what = 'snerf_mlp_pack'
                 st = lib.snerf_mlp_pack(ctypes.byref(self.desc), arr, len(held), _ptr(self.buffer), _stream())
             else:
+                what = 'snerf_mlp_pack_for'
                 st = lib.snerf_mlp_pack_for(ctypes.byref(self.desc), arr, len(held), _ptr(self.buffer), int(precision),
                                             1 if training else 0, _stream())
-        _lib.check(st, 'snerf_mlp_pack')
+        _lib.check(st, what)
 
     def forward(self, origins: Tensor, dirs: Tensor, view_dirs: Optional[Tensor], depths: Tensor,
-                sigma_noise: Optional[Tensor] = None, precision: int = 0):
-        """-> sigma (n,S,1), rgb (n,S,3).  precision: PRECISION_FP32 (0) or PRECISION_F16X3 (1), see the C header."""
+                sigma_noise: Optional[Tensor] = None, precision: int = PRECISION_FP32):
+        """-> sigma (n,S,1), rgb (n,S,3).  precision: a PRECISION_* value (enum snerf_precision), see the C header."""
         lib = _lib.load()
         n, s = depths.shape
         origins = _dev(origins, 'origins', (n, 3))
@@ -215,7 +237,7 @@ class PackedMlp:
 
     # ---- training ------------------------------------------------------------------------------------------
     def forward_train(self, origins: Tensor, dirs: Tensor, view_dirs: Optional[Tensor], depths: Tensor,
-                      sigma_noise: Optional[Tensor] = None, precision: int = 0):
+                      sigma_noise: Optional[Tensor] = None, precision: int = PRECISION_FP32):
         """Forward that also keeps every layer's input for backward().  -> sigma (n,S,1), rgb (n,S,3), saved"""
         lib = _lib.load()
         n, s = depths.shape
@@ -244,7 +266,7 @@ class PackedMlp:
         return int(_lib.load().snerf_mlp_backward_workspace_floats(ctypes.byref(self.desc), n, s))
 
     def backward(self, saved: Tensor, sigma: Tensor, rgb: Tensor, d_sigma: Tensor, d_rgb: Tensor,
-                 param_shapes: List[tuple], precision: int = 0, into: Optional[List[Tensor]] = None,
+                 param_shapes: List[tuple], precision: int = PRECISION_FP32, into: Optional[List[Tensor]] = None,
                  work: Optional[Tensor] = None) -> List[Tensor]:
         """dL/dparam for every parameter (C-ABI order), given dL/dsigma (n,S[,1]) and dL/drgb (n,S,3).  ``into``: existing
         gradient tensors to ADD to (the kernel accumulates; no separate add launches) instead of fresh ones.  ``work``: the
@@ -474,7 +496,6 @@ def composite(sigma: Tensor, rgb: Tensor, depths: Tensor, march_dirs: Tensor, nd
               per_sample: bool = True) -> Dict[str, Tensor]:
     """Keys as the reference's volume_rendering: rgb, acc, alpha, visibility, weights, depth, depth_var
     (+ depth_ndc, depth_var_ndc when ndc).  per_sample=False skips alpha/visibility/weights."""
-    lib = _lib.load()
     n, s = depths.shape
     sigma = _dev(sigma.reshape(n, s), 'sigma', (n, s))
     rgb = _dev(rgb, 'rgb', (n, s, 3))
@@ -492,13 +513,10 @@ def composite(sigma: Tensor, rgb: Tensor, depths: Tensor, march_dirs: Tensor, nd
         rays_d = _dev(rays_d, 'rays_d', (n, 3))
     if n == 0:
         return out
-    with torch.cuda.device(dev):
-        st = lib.snerf_composite(_ptr(sigma), _ptr(rgb), _ptr(depths), _ptr(march_dirs), _ptr(rays_o if ndc else None),
-                                 _ptr(rays_d if ndc else None), n, s, int(bool(ndc)), int(bool(white_bkgd)),
-                                 _ptr(out['rgb']), _ptr(out['acc']), _ptr(out.get('alpha')), _ptr(out.get('visibility')),
-                                 _ptr(out.get('weights')), _ptr(out['depth']), _ptr(out['depth_var']),
-                                 _ptr(out.get('depth_ndc')), _ptr(out.get('depth_var_ndc')), _stream())
-    _lib.check(st, 'snerf_composite')
+    _enqueue('snerf_composite', dev, _ptr(sigma), _ptr(rgb), _ptr(depths), _ptr(march_dirs), _ptr(rays_o if ndc else None),
+             _ptr(rays_d if ndc else None), n, s, int(bool(ndc)), int(bool(white_bkgd)), _ptr(out['rgb']), _ptr(out['acc']),
+             _ptr(out.get('alpha')), _ptr(out.get('visibility')), _ptr(out.get('weights')), _ptr(out['depth']),
+             _ptr(out['depth_var']), _ptr(out.get('depth_ndc')), _ptr(out.get('depth_var_ndc')))
     return out
 
 
@@ -507,7 +525,6 @@ def composite_backward(sigma: Tensor, rgb: Tensor, depths: Tensor, march_dirs: T
                        rays_o: Optional[Tensor], rays_d: Optional[Tensor], grad_rgb: Optional[Tensor],
                        grad_acc: Optional[Tensor], grad_depth: Optional[Tensor], grad_depth_ndc: Optional[Tensor]):
     """-> d_sigma (n,S), d_rgb (n,S,3) from the per-ray gradients (None = zero)."""
-    lib = _lib.load()
     n, s = depths.shape
     sigma = _dev(sigma.reshape(n, s), 'sigma', (n, s))
     rgb = _dev(rgb, 'rgb', (n, s, 3))
@@ -525,18 +542,14 @@ def composite_backward(sigma: Tensor, rgb: Tensor, depths: Tensor, march_dirs: T
     d_rgb = torch.empty((n, s, 3), dtype=torch.float32, device=dev)
     if n == 0:
         return d_sigma, d_rgb
-    with torch.cuda.device(dev):
-        st = lib.snerf_composite_backward(_ptr(sigma), _ptr(rgb), _ptr(depths), _ptr(march_dirs),
-                                          _ptr(rays_o if ndc else None), _ptr(rays_d if ndc else None), n, s,
-                                          int(bool(ndc)), int(bool(white_bkgd)), _ptr(grad_rgb), _ptr(grad_acc),
-                                          _ptr(grad_depth), _ptr(grad_depth_ndc), _ptr(d_sigma), _ptr(d_rgb), _stream())
-    _lib.check(st, 'snerf_composite_backward')
+    _enqueue('snerf_composite_backward', dev, _ptr(sigma), _ptr(rgb), _ptr(depths), _ptr(march_dirs),
+             _ptr(rays_o if ndc else None), _ptr(rays_d if ndc else None), n, s, int(bool(ndc)), int(bool(white_bkgd)),
+             _ptr(grad_rgb), _ptr(grad_acc), _ptr(grad_depth), _ptr(grad_depth_ndc), _ptr(d_sigma), _ptr(d_rgb))
     return d_sigma, d_rgb
 
 
 # ---------------------------------------------------------------------------------------------- K5
 def resample_depths(depths_coarse: Tensor, weights_coarse: Tensor, num_fine: int, u: Optional[Tensor] = None) -> Tensor:
-    lib = _lib.load()
     n, s_c = depths_coarse.shape
     depths_coarse = _dev(depths_coarse, 'depths_coarse')
     weights_coarse = _dev(weights_coarse, 'weights_coarse', (n, s_c))
@@ -544,10 +557,8 @@ def resample_depths(depths_coarse: Tensor, weights_coarse: Tensor, num_fine: int
     out = torch.empty((n, s_c + num_fine), dtype=torch.float32, device=depths_coarse.device)
     if n == 0:
         return out
-    with torch.cuda.device(depths_coarse.device):
-        st = lib.snerf_resample_depths(_ptr(depths_coarse), _ptr(weights_coarse), n, s_c, int(num_fine), _ptr(u),
-                                       _ptr(out), _stream())
-    _lib.check(st, 'snerf_resample_depths')
+    _enqueue('snerf_resample_depths', depths_coarse.device, _ptr(depths_coarse), _ptr(weights_coarse), n, s_c, int(num_fine),
+             _ptr(u), _ptr(out))
     return out
 
 
@@ -555,7 +566,6 @@ def resample_depths(depths_coarse: Tensor, weights_coarse: Tensor, num_fine: int
 def to_display(rgb: Optional[Tensor], depth: Optional[Tensor] = None, colour: bool = True):
     """-> uint8 image (n,3) [clip to [0,1], round(255 x) half-to-even] and depth clipped at 0 (or None).
     ``colour=False`` converts only the depth column (image is None)."""
-    lib = _lib.load()
     n = rgb.shape[0] if colour else depth.shape[0]
     rgb = _dev(rgb, 'rgb', (n, 3)) if colour else None
     depth = _dev(depth, 'depth', (n,))
@@ -564,10 +574,8 @@ def to_display(rgb: Optional[Tensor], depth: Optional[Tensor] = None, colour: bo
     depth_out = None if depth is None else torch.empty((n,), dtype=torch.float32, device=dev)
     if n == 0:
         return image, depth_out
-    with torch.cuda.device(dev):
-        st = lib.snerf_to_display(_ptr(rgb), _ptr(depth), n, ctypes.c_void_p(0 if image is None else image.data_ptr()),
-                                  _ptr(depth_out), _stream())
-    _lib.check(st, 'snerf_to_display')
+    _enqueue('snerf_to_display', dev, _ptr(rgb), _ptr(depth), n, ctypes.c_void_p(0 if image is None else image.data_ptr()),
+             _ptr(depth_out))
     return image, depth_out
 
 
@@ -586,17 +594,10 @@ def _typed(t, name: str, dtypes, shape=None) -> Tensor:
 
 SSIM_WINDOW = 11     # taps of the Gaussian window (sigma 1.5, truncate 3.5): the shortest side an image may have
 
-# scratch of the metric reductions (per-workgroup partial sums), one per device, grown on demand; calls on one device are
-# ordered by the stream they are enqueued on
-_metric_workspaces: Dict[torch.device, Tensor] = {}
 
-
-def _metric_workspace(lib, dev: torch.device, height: int, width: int) -> Tensor:
-    need = int(lib.snerf_metrics_workspace_bytes(int(height), int(width)))
-    ws = _metric_workspaces.get(dev)
-    if ws is None or ws.numel() < need:
-        ws = _metric_workspaces[dev] = torch.empty((need,), dtype=torch.uint8, device=dev)
-    return ws
+def _metric_workspace(dev: torch.device, height: int, width: int) -> Tensor:
+    """Scratch of the metric reductions (per-workgroup partial sums)."""
+    return _workspace('metric', dev, int(_lib.load().snerf_metrics_workspace_bytes(int(height), int(width))))
 
 
 def _image_pair(gt: Tensor, image: Tensor, mask: Optional[Tensor]):
@@ -616,11 +617,8 @@ def image_error_sums(gt: Tensor, image: Tensor, mask: Optional[Tensor] = None) -
     if h < 1 or w < 1:
         raise RuntimeError(f'gt_image: empty image {tuple(gt.shape)}')
     sums = torch.empty((3,), dtype=torch.int64, device=gt.device)
-    lib = _lib.load()
-    with torch.cuda.device(gt.device):
-        ws = _metric_workspace(lib, gt.device, h, w)
-        st = lib.snerf_image_error_sums(_ptr(gt), _ptr(image), _ptr(mask), h, w, _ptr(sums), _ptr(ws), _stream())
-    _lib.check(st, 'snerf_image_error_sums')
+    _enqueue('snerf_image_error_sums', gt.device, _ptr(gt), _ptr(image), _ptr(mask), h, w, _ptr(sums),
+             _ptr(_metric_workspace(gt.device, h, w)))
     return sums
 
 
@@ -633,11 +631,8 @@ def ssim_sums(gt: Tensor, image: Tensor, mask: Optional[Tensor] = None, return_m
                            f'at least {SSIM_WINDOW}')
     sums = torch.empty((2,), dtype=torch.float64, device=gt.device)
     s_map = torch.empty((h, w, 3), dtype=torch.float64, device=gt.device) if return_map else None
-    lib = _lib.load()
-    with torch.cuda.device(gt.device):
-        ws = _metric_workspace(lib, gt.device, h, w)
-        st = lib.snerf_ssim_sums(_ptr(gt), _ptr(image), _ptr(mask), h, w, _ptr(sums), _ptr(s_map), _ptr(ws), _stream())
-    _lib.check(st, 'snerf_ssim_sums')
+    _enqueue('snerf_ssim_sums', gt.device, _ptr(gt), _ptr(image), _ptr(mask), h, w, _ptr(sums), _ptr(s_map),
+             _ptr(_metric_workspace(gt.device, h, w)))
     return (sums, s_map) if return_map else sums
 
 
@@ -655,12 +650,8 @@ def depth_error_sums(gt: Tensor, depth: Tensor, gt_scale: float = 1.0, eval_scal
     if sorted_gt is not None:
         sorted_gt = _typed(sorted_gt, 'sorted_gt', (torch.float32,), (n,))
     sums = torch.full((4,), float('nan'), dtype=torch.float64, device=gt.device)
-    lib = _lib.load()
-    with torch.cuda.device(gt.device):
-        ws = _metric_workspace(lib, gt.device, 1, 1)
-        st = lib.snerf_depth_error_sums(_ptr(gt), _ptr(depth), float(gt_scale), float(eval_scale), _ptr(mask), n, _ptr(sorted_gt),
-                                        _ptr(sums), _ptr(ws), _stream())
-    _lib.check(st, 'snerf_depth_error_sums')
+    _enqueue('snerf_depth_error_sums', gt.device, _ptr(gt), _ptr(depth), float(gt_scale), float(eval_scale), _ptr(mask), n,
+             _ptr(sorted_gt), _ptr(sums), _ptr(_metric_workspace(gt.device, 1, 1)))
     return sums
 
 
@@ -674,18 +665,13 @@ def rank_correlation_sums(x: Tensor, y: Tensor, sorted_x: Tensor, sorted_y: Tens
     sorted_x = _typed(sorted_x, 'sorted_x', (torch.float32,), (n,))
     sorted_y = _typed(sorted_y, 'sorted_y', (torch.float32,), (n,))
     sums = torch.empty((3,), dtype=torch.float64, device=x.device)
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        ws = _metric_workspace(lib, x.device, 1, 1)
-        st = lib.snerf_rank_correlation_sums(_ptr(x), _ptr(y), _ptr(sorted_x), _ptr(sorted_y), n, _ptr(sums), _ptr(ws), _stream())
-    _lib.check(st, 'snerf_rank_correlation_sums')
+    _enqueue('snerf_rank_correlation_sums', x.device, _ptr(x), _ptr(y), _ptr(sorted_x), _ptr(sorted_y), n, _ptr(sums),
+             _ptr(_metric_workspace(x.device, 1, 1)))
     return sums
 
 
 # ---------------------------------------------------------------------------------------------- Q2 visibility masks
 VISIBILITY_CAMERA = 30     # doubles per training view: inv(K_train) 3x3 | rows 0..2 of E_test inv(E_train) 3x4 | K_test 3x3
-
-_visibility_workspaces: Dict[torch.device, Tensor] = {}
 
 
 def _visibility_extent(views: int, h: int, w: int, name: str) -> int:
@@ -710,15 +696,9 @@ def visibility_mask_project(depth_train: Tensor, cameras: Tensor):
     points = torch.empty((views, 3, h, w), dtype=torch.float64, device=dev)
     keys = torch.empty((views, h, w), dtype=torch.int32, device=dev)
     stats = torch.empty((views, 2), dtype=torch.float64, device=dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        need = int(lib.snerf_visibility_mask_workspace_bytes(views, h, w))
-        ws = _visibility_workspaces.get(dev)
-        if ws is None or ws.numel() < need:
-            ws = _visibility_workspaces[dev] = torch.empty((need,), dtype=torch.uint8, device=dev)
-        st = lib.snerf_visibility_mask_project(_ptr(depth_train), _ptr(cameras), views, h, w, _ptr(points), _ptr(keys), _ptr(stats),
-                                               _ptr(ws), _stream())
-    _lib.check(st, 'snerf_visibility_mask_project')
+    ws = _workspace('visibility', dev, int(_lib.load().snerf_visibility_mask_workspace_bytes(views, h, w)))
+    _enqueue('snerf_visibility_mask_project', dev, _ptr(depth_train), _ptr(cameras), views, h, w, _ptr(points), _ptr(keys),
+             _ptr(stats), _ptr(ws))
     return points, keys, stats
 
 
@@ -728,10 +708,7 @@ def visibility_mask_list_starts(sorted_keys: Tensor, views: int, h: int, w: int)
     per_view = _visibility_extent(views, h, w, 'sorted_keys')
     sorted_keys = _typed(sorted_keys, 'sorted_keys', (torch.int32,), (views * h * w,))
     starts = torch.empty((views * per_view + 1,), dtype=torch.int32, device=sorted_keys.device)
-    lib = _lib.load()
-    with torch.cuda.device(sorted_keys.device):
-        st = lib.snerf_visibility_mask_list_starts(_ptr(sorted_keys), views, h, w, _ptr(starts), _stream())
-    _lib.check(st, 'snerf_visibility_mask_list_starts')
+    _enqueue('snerf_visibility_mask_list_starts', sorted_keys.device, _ptr(sorted_keys), views, h, w, _ptr(starts))
     return starts
 
 
@@ -753,12 +730,8 @@ def visibility_mask_gather(points: Tensor, order: Tensor, starts: Tensor, stats:
     mask_views = torch.empty((views, h, w), dtype=torch.uint8, device=dev)
     warped = torch.empty((views, h, w), dtype=torch.float64, device=dev) if return_views else None
     weights = torch.empty((views, h, w), dtype=torch.float64, device=dev) if return_views else None
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        st = lib.snerf_visibility_mask_gather(_ptr(points), _ptr(order), _ptr(starts), _ptr(stats), _ptr(depth_test),
-                                              float(depth_error_threshold), views, h, w, _ptr(mask_views), _ptr(warped), _ptr(weights),
-                                              _stream())
-    _lib.check(st, 'snerf_visibility_mask_gather')
+    _enqueue('snerf_visibility_mask_gather', dev, _ptr(points), _ptr(order), _ptr(starts), _ptr(stats), _ptr(depth_test),
+             float(depth_error_threshold), views, h, w, _ptr(mask_views), _ptr(warped), _ptr(weights))
     return (mask_views, warped, weights) if return_views else mask_views
 
 
@@ -772,26 +745,17 @@ def visibility_mask_combine(mask_views: Tensor, min_views: int = 2) -> Tensor:
     if not 1 <= int(min_views) <= views:
         raise RuntimeError(f'min_views: expected 1..{views} (the number of training views), got {min_views}')
     mask = torch.empty((h, w), dtype=torch.bool, device=mask_views.device)
-    lib = _lib.load()
-    with torch.cuda.device(mask_views.device):
-        st = lib.snerf_visibility_mask_combine(_ptr(mask_views), views, h, w, int(min_views), _ptr(mask), _stream())
-    _lib.check(st, 'snerf_visibility_mask_combine')
+    _enqueue('snerf_visibility_mask_combine', mask_views.device, _ptr(mask_views), views, h, w, int(min_views), _ptr(mask))
     return mask
 
 
 # ---------------------------------------------------------------------------------------------- Q4 sorts and mask compaction
 SORT_MAX_COUNT = 2 ** 31 - 1
 
-# scratch of the sorts and the compaction (second key / index buffers, digit counters), one per device, grown on demand; calls on
-# one device are ordered by the stream they are enqueued on
-_sort_workspaces: Dict[torch.device, Tensor] = {}
-
 
 def _sort_workspace(dev: torch.device, need: int) -> Tensor:
-    ws = _sort_workspaces.get(dev)
-    if ws is None or ws.numel() < need:
-        ws = _sort_workspaces[dev] = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
-    return ws
+    """Scratch of the sorts and the compaction (second key / index buffers, digit counters); never an empty tensor."""
+    return _workspace('sort', dev, max(need, 1))
 
 
 def _flat(t: Tensor, name: str) -> int:
@@ -810,11 +774,8 @@ def sort_values(x: Tensor) -> Tensor:
     out = torch.empty_like(x)
     if n == 0:
         return out
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        ws = _sort_workspace(x.device, int(lib.snerf_sort_workspace_bytes(n, 32)))
-        st = lib.snerf_sort_f32(_ptr(x), n, _ptr(out), _ptr(ws), _stream())
-    _lib.check(st, 'snerf_sort_f32')
+    ws = _sort_workspace(x.device, int(_lib.load().snerf_sort_workspace_bytes(n, 32)))
+    _enqueue('snerf_sort_f32', x.device, _ptr(x), n, _ptr(out), _ptr(ws))
     return out
 
 
@@ -832,11 +793,8 @@ def sort_keys_with_order(keys: Tensor, key_bits: Optional[int] = None):
     order = torch.empty((n,), dtype=torch.int64, device=keys.device)
     if n == 0:
         return sorted_keys, order
-    lib = _lib.load()
-    with torch.cuda.device(keys.device):
-        ws = _sort_workspace(keys.device, int(lib.snerf_sort_workspace_bytes(n, int(key_bits))))
-        st = lib.snerf_sort_keys_with_order(_ptr(keys), n, int(key_bits), _ptr(sorted_keys), _ptr(order), _ptr(ws), _stream())
-    _lib.check(st, 'snerf_sort_keys_with_order')
+    ws = _sort_workspace(keys.device, int(_lib.load().snerf_sort_workspace_bytes(n, int(key_bits))))
+    _enqueue('snerf_sort_keys_with_order', keys.device, _ptr(keys), n, int(key_bits), _ptr(sorted_keys), _ptr(order), _ptr(ws))
     return sorted_keys, order
 
 
@@ -849,17 +807,14 @@ def compact_pair(a: Tensor, b: Tensor, mask: Tensor):
     mask = _typed(mask, 'mask', (torch.bool, torch.uint8), (n,))
     a_kept, b_kept = torch.empty_like(a), torch.empty_like(b)
     kept = torch.empty((1,), dtype=torch.int64, device=a.device)
-    lib = _lib.load()
-    with torch.cuda.device(a.device):
-        ws = _sort_workspace(a.device, int(lib.snerf_compact_workspace_bytes(n)))
-        st = lib.snerf_compact_f32_pair(_ptr(a), _ptr(b), _ptr(mask), n, _ptr(a_kept), _ptr(b_kept), _ptr(kept), _ptr(ws), _stream())
-    _lib.check(st, 'snerf_compact_f32_pair')
+    ws = _sort_workspace(a.device, int(_lib.load().snerf_compact_workspace_bytes(n)))
+    _enqueue('snerf_compact_f32_pair', a.device, _ptr(a), _ptr(b), _ptr(mask), n, _ptr(a_kept), _ptr(b_kept), _ptr(kept), _ptr(ws))
     count = int(kept.item())
     return a_kept[:count], b_kept[:count]
 
 
 # ---------------------------------------------------------------------------------------------- Q5 the Warper
-WARP_U8, WARP_F32, WARP_F64 = 0, 1, 2      # enum SNERF_WARP_*
+WARP_U8, WARP_F32, WARP_F64 = C.SNERF_WARP_U8, C.SNERF_WARP_F32, C.SNERF_WARP_F64
 _WARP_TYPES = {torch.uint8: WARP_U8, torch.float32: WARP_F32, torch.float64: WARP_F64}
 WARP_MAX_CHANNELS = 4
 
@@ -893,14 +848,9 @@ def _warp_together(dev: torch.device, **operands) -> None:
             raise RuntimeError(f'{name}: expected a tensor on {dev}, the device of the call\'s first operand, got one on {t.device}')
 
 
-# the projection's scratch (per-workgroup maxima) is the masks' buffer, _visibility_workspaces: one per device, grown on demand;
-# every call writes it before it reads it, and calls on one device are ordered by the stream they are enqueued on
-def _warp_workspace(lib, dev: torch.device, h: int, w: int) -> Tensor:
-    need = int(lib.snerf_warp_workspace_bytes(h, w))
-    ws = _visibility_workspaces.get(dev)
-    if ws is None or ws.numel() < need:
-        ws = _visibility_workspaces[dev] = torch.empty((need,), dtype=torch.uint8, device=dev)
-    return ws
+def _warp_workspace(dev: torch.device, h: int, w: int) -> Tensor:
+    """The projection's scratch (per-workgroup maxima): on purpose the masks' buffer, kind 'visibility'."""
+    return _workspace('visibility', dev, int(_lib.load().snerf_warp_workspace_bytes(h, w)))
 
 
 def warp_project(depth1: Tensor, camera: Tensor, mask1: Optional[Tensor] = None):
@@ -920,12 +870,8 @@ def warp_project(depth1: Tensor, camera: Tensor, mask1: Optional[Tensor] = None)
     keys = torch.empty((1, h, w), dtype=torch.int32, device=dev)
     stats = torch.empty((1, 2), dtype=torch.float64, device=dev)
     flow12 = torch.empty((h, w, 2), dtype=torch.float64, device=dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        ws = _warp_workspace(lib, dev, h, w)
-        st = lib.snerf_warp_project(_ptr(depth1), _ptr(camera), _ptr(mask1), h, w, _ptr(points), _ptr(keys), _ptr(stats), _ptr(flow12),
-                                    _ptr(ws), _stream())
-    _lib.check(st, 'snerf_warp_project')
+    _enqueue('snerf_warp_project', dev, _ptr(depth1), _ptr(camera), _ptr(mask1), h, w, _ptr(points), _ptr(keys), _ptr(stats),
+             _ptr(flow12), _ptr(_warp_workspace(dev, h, w)))
     return points, keys, stats, flow12
 
 
@@ -945,12 +891,8 @@ def warp_positions_from_flow(flow12: Tensor, depth1: Tensor, mask1: Optional[Ten
     points = torch.empty((1, 3, h, w), dtype=torch.float64, device=dev)
     keys = torch.empty((1, h, w), dtype=torch.int32, device=dev)
     stats = torch.empty((1, 2), dtype=torch.float64, device=dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        ws = _warp_workspace(lib, dev, h, w)
-        st = lib.snerf_warp_positions_from_flow(_ptr(flow12), _ptr(depth1), _WARP_TYPES[depth1.dtype], _ptr(mask1), _ptr(flow12_mask), h, w,
-                                                _ptr(points), _ptr(keys), _ptr(stats), _ptr(ws), _stream())
-    _lib.check(st, 'snerf_warp_positions_from_flow')
+    _enqueue('snerf_warp_positions_from_flow', dev, _ptr(flow12), _ptr(depth1), _WARP_TYPES[depth1.dtype], _ptr(mask1),
+             _ptr(flow12_mask), h, w, _ptr(points), _ptr(keys), _ptr(stats), _ptr(_warp_workspace(dev, h, w)))
     return points, keys, stats
 
 
@@ -971,11 +913,8 @@ def warp_splat_gather(points: Tensor, order: Tensor, starts: Tensor, stats: Tens
     _warp_together(dev, order=order, starts=starts, stats=stats, values=values)
     warped = torch.empty((h, w, c), dtype=torch.uint8 if is_image else torch.float64, device=dev)
     mask2 = torch.empty((h, w), dtype=torch.bool, device=dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        st = lib.snerf_warp_splat_gather(_ptr(points), _ptr(order), _ptr(starts), _ptr(stats), _ptr(values), _WARP_TYPES[values.dtype], c,
-                                         int(bool(is_image)), h, w, _ptr(warped), _ptr(mask2), _stream())
-    _lib.check(st, 'snerf_warp_splat_gather')
+    _enqueue('snerf_warp_splat_gather', dev, _ptr(points), _ptr(order), _ptr(starts), _ptr(stats), _ptr(values),
+             _WARP_TYPES[values.dtype], c, int(bool(is_image)), h, w, _ptr(warped), _ptr(mask2))
     return warped, mask2
 
 
@@ -990,11 +929,8 @@ def warp_interpolate(frame2: Tensor, flow12: Tensor, mask2: Optional[Tensor] = N
     _warp_together(dev, flow12=flow12, mask2=mask2, flow12_mask=flow12_mask)
     warped = torch.empty((h, w, c), dtype=torch.uint8 if is_image else torch.float64, device=dev)
     mask1 = torch.empty((h, w), dtype=torch.bool, device=dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        st = lib.snerf_warp_interpolate(_ptr(frame2), _WARP_TYPES[frame2.dtype], c, _ptr(mask2), _ptr(flow12), _ptr(flow12_mask),
-                                        int(bool(is_image)), h, w, _ptr(warped), _ptr(mask1), _stream())
-    _lib.check(st, 'snerf_warp_interpolate')
+    _enqueue('snerf_warp_interpolate', dev, _ptr(frame2), _WARP_TYPES[frame2.dtype], c, _ptr(mask2), _ptr(flow12),
+             _ptr(flow12_mask), int(bool(is_image)), h, w, _ptr(warped), _ptr(mask1))
     return warped, mask1
 
 
@@ -1024,11 +960,6 @@ def _mask(t: Optional[Tensor], name: str, n: int) -> Optional[Tensor]:
     if not t.is_cuda or t.dtype not in (torch.bool, torch.uint8) or tuple(t.shape) != (n,):
         raise RuntimeError(f'{name}: expected a bool/uint8 GPU tensor of shape ({n},), got {t.dtype} {tuple(t.shape)} on {t.device}')
     return t.contiguous()
-
-
-# scratch of snerf_loss_forward (block partials + completion counter), one per device; calls on one device are ordered
-# by the stream they are enqueued on -- callers that evaluate losses on several streams at once need one buffer each
-_loss_workspaces: Dict[torch.device, Tensor] = {}
 
 
 def _loss_table(terms: List[LossTermSpec], grads: Optional[List[Optional[Tensor]]],
@@ -1065,9 +996,9 @@ def loss_forward(terms: List[LossTermSpec], num_groups: int):
         raise RuntimeError('fused loss: every term must cover the same rays')
     values = torch.empty((count + num_groups + 1,), dtype=torch.float32, device=dev)
     scales = torch.empty((count,), dtype=torch.float32, device=dev)
-    ws = _loss_workspaces.get(dev)
-    if ws is None:
-        ws = _loss_workspaces[dev] = torch.zeros((int(lib.snerf_loss_workspace_bytes()),), dtype=torch.uint8, device=dev)
+    # block partials + a completion counter that must be zero on first use (the kernel leaves it zero again); callers that
+    # evaluate losses on several streams of one device at once need one buffer each
+    ws = _workspace('loss', dev, int(lib.snerf_loss_workspace_bytes()), zeroed=True)
     with torch.cuda.device(dev):
         st = lib.snerf_loss_forward(_loss_table(terms, None), count, int(num_groups), n, _ptr(values), _ptr(scales),
                                     ctypes.c_void_p(ws.data_ptr()), _stream())
@@ -1111,7 +1042,6 @@ def patch_consistency_masks(rays_o: Tensor, rays_d: Tensor, depth1: Tensor, dept
                             pixel_id: Tensor, poses: Tensor, intrinsic: Tensor, images: Tensor, patch_size,
                             rmse_threshold: float, with_rmse: bool = False):
     """Decision masks of the patch-reprojection consistency losses: (mask1, mask2[, rmse1, rmse2]) per ray."""
-    lib = _lib.load()
     n = rays_o.shape[0]
     v, h, w, c = images.shape
     if c != 3:
@@ -1130,7 +1060,8 @@ def patch_consistency_masks(rays_o: Tensor, rays_d: Tensor, depth1: Tensor, dept
     rmse1 = torch.empty((n,), dtype=torch.float32, device=dev) if with_rmse else None
     rmse2 = torch.empty((n,), dtype=torch.float32, device=dev) if with_rmse else None
     if n > 0:
-        with torch.cuda.device(dev):
+        lib = _lib.load()
+        with torch.cuda.device(dev):      # (inline, not _enqueue: three times per training iteration)
             st = lib.snerf_patch_consistency_masks(
                 _ptr(rays_o), _ptr(rays_d), _ptr(depth1), _ptr(depth2), _ptr(ray_mask), _ptr(pixel_id), n, _ptr(poses),
                 _ptr(intrinsic), _ptr(images), v, h, w, int(patch_size[0]), int(patch_size[1]), float(rmse_threshold),
@@ -1172,13 +1103,11 @@ def adam_step(params: List[Tensor], grads: List[Optional[Tensor]], exp_avg: List
 # ---------------------------------------------------------------------------------------------- f2 batch assembly
 def camera_table(intrinsics: Tensor, poses: Tensor, resolution) -> Tensor:
     """(V, 24) per-view camera constants (inverse intrinsic, rotation, origin, NDC factors) on the device."""
-    lib = _lib.load()
     v = poses.shape[0]
     intrinsics, poses = _dev(intrinsics, 'intrinsics', (v, 3, 3)), _dev(poses, 'poses', (v, 4, 4))
     table = torch.empty((v, _lib.CAMERA_FLOATS), dtype=torch.float32, device=poses.device)
-    with torch.cuda.device(poses.device):
-        st = lib.snerf_camera_table(_ptr(intrinsics), _ptr(poses), v, int(resolution[0]), int(resolution[1]), _ptr(table), _stream())
-    _lib.check(st, 'snerf_camera_table')
+    _enqueue('snerf_camera_table', poses.device, _ptr(intrinsics), _ptr(poses), v, int(resolution[0]), int(resolution[1]),
+             _ptr(table))
     return table
 
 
@@ -1270,7 +1199,6 @@ def gather_dense_depth(indices: Tensor, num_pixel_rays: int, depths: Tensor, wei
 def scene_images(images: Tensor, white_bkgd: bool = False) -> Tensor:
     """One launch: (..., C) uint8 images on the device, C = 3 or 4 -> (..., 3) float32, ``u8 / 255`` and, with ``white_bkgd``,
     ``rgb * a + (1 - a)`` over the last channel (the reference's preprocess_images)."""
-    lib = _lib.load()
     images = _typed(images, 'images', (torch.uint8,))
     if images.dim() < 2 or images.shape[-1] not in (3, 4):
         raise RuntimeError(f'images: expected (..., 3) or (..., 4), got {tuple(images.shape)}')
@@ -1279,9 +1207,7 @@ def scene_images(images: Tensor, white_bkgd: bool = False) -> Tensor:
     pixels = images.numel() // channels
     if pixels == 0:
         return out
-    with torch.cuda.device(images.device):
-        st = lib.snerf_scene_images(_ptr(images), pixels, channels, int(bool(white_bkgd)), _ptr(out), _stream())
-    _lib.check(st, 'snerf_scene_images')
+    _enqueue('snerf_scene_images', images.device, _ptr(images), pixels, channels, int(bool(white_bkgd)), _ptr(out))
     return out
 
 
@@ -1343,18 +1269,15 @@ def rasterise_sparse_depth(x, y, depth, reprojection_error, view, num_views: int
     if table is not None:
         out['depths_ndc'] = f()
     workspace = torch.empty((int(lib.snerf_rasterise_sparse_depth_workspace_bytes(v, h, w)),), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        st = lib.snerf_rasterise_sparse_depth(_ptr(px), _ptr(py), _ptr(pd), _ptr(pe), _ptr(pv), count, float(scale), float(divisor),
-                                              _ptr(table), float(near), v, h, w, _ptr(out['depths']), _ptr(out['errors']),
-                                              _ptr(out.get('depths_ndc')), _ptr(workspace), _stream())
-    _lib.check(st, 'snerf_rasterise_sparse_depth')
+    _enqueue('snerf_rasterise_sparse_depth', dev, _ptr(px), _ptr(py), _ptr(pd), _ptr(pe), _ptr(pv), count, float(scale),
+             float(divisor), _ptr(table), float(near), v, h, w, _ptr(out['depths']), _ptr(out['errors']),
+             _ptr(out.get('depths_ndc')), _ptr(workspace))
     return out
 
 
 def depth_table_to_ndc(depths: Tensor, table: Tensor, resolution, near: float) -> Tensor:
     """One launch: the reference's convert_depth_to_ndc over a per-pixel depth table (num_views*h*w entries, any shape) with the
     rays recomputed from the camera ``table``; -1 stays -1.  Returns a tensor of the input's shape."""
-    lib = _lib.load()
     h, w = int(resolution[0]), int(resolution[1])
     v = table.shape[0]
     table = _dev(table, 'camera table', (v, _lib.CAMERA_FLOATS))
@@ -1362,9 +1285,7 @@ def depth_table_to_ndc(depths: Tensor, table: Tensor, resolution, near: float) -
     if depths.numel() != v * h * w:
         raise RuntimeError(f'depths: {depths.numel()} entries, expected {v}*{h}*{w} (one per pixel)')
     out = torch.empty_like(depths)
-    with torch.cuda.device(depths.device):
-        st = lib.snerf_depth_table_to_ndc(_ptr(depths), _ptr(table), v, h, w, float(near), _ptr(out), _stream())
-    _lib.check(st, 'snerf_depth_table_to_ndc')
+    _enqueue('snerf_depth_table_to_ndc', depths.device, _ptr(depths), _ptr(table), v, h, w, float(near), _ptr(out))
     return out
 
 
@@ -1486,11 +1407,8 @@ class IterationRing:
         return slot
 
     def advance(self) -> None:
-        lib = _lib.load()
-        with torch.cuda.device(self.device):
-            st = lib.snerf_iteration_advance(ctypes.c_void_p(self.ring.data_ptr()), self.slots, ctypes.c_void_p(self.counter.data_ptr()),
-                                             ctypes.c_void_p(self.current.data_ptr()), _stream())
-        _lib.check(st, 'snerf_iteration_advance')
+        _enqueue('snerf_iteration_advance', self.device, ctypes.c_void_p(self.ring.data_ptr()), self.slots,
+                 ctypes.c_void_p(self.counter.data_ptr()), ctypes.c_void_p(self.current.data_ptr()))
 
 
 # ---------------------------------------------------------------------------------------------- Q3 LPIPS
@@ -1503,10 +1421,8 @@ LPIPS_VGG_CONVS = ((64, 3, 3), (64, 64, 3), (128, 64, 3), (128, 128, 3), (256, 1
                    (512, 512, 3), (512, 512, 3), (512, 512, 3), (512, 512, 3), (512, 512, 3))
 LPIPS_VGG_TAP_CONVS = (1, 3, 6, 9, 12)
 # net -> (the C ABI's selector, the name in messages, minimum extent, convolutions, the convolution each tap follows)
-_LPIPS_NETS = {'alex': (0, 'AlexNet', LPIPS_MIN_EXTENT, LPIPS_CONVS, (0, 1, 2, 3, 4)),
-               'vgg': (1, 'VGG-16', LPIPS_VGG_MIN_EXTENT, LPIPS_VGG_CONVS, LPIPS_VGG_TAP_CONVS)}
-
-_lpips_workspaces: Dict[tuple, Tensor] = {}      # one per (device, network)
+_LPIPS_NETS = {'alex': (C.SNERF_LPIPS_ALEX, 'AlexNet', LPIPS_MIN_EXTENT, LPIPS_CONVS, (0, 1, 2, 3, 4)),
+               'vgg': (C.SNERF_LPIPS_VGG16, 'VGG-16', LPIPS_VGG_MIN_EXTENT, LPIPS_VGG_CONVS, LPIPS_VGG_TAP_CONVS)}
 
 
 def _lpips_net(net):
@@ -1557,7 +1473,7 @@ def lpips_pack(conv_weights, conv_biases, lin_weights, shift=None, scale=None, n
     with torch.cuda.device(dev):
         st = lib.snerf_lpips_net_pack(selector, _pointer_array(weights), _pointer_array(biases), _pointer_array(lins), scaling, _ptr(packed),
                                       _stream())
-    _lib.check(st, 'snerf_lpips_pack')
+    _lib.check(st, 'snerf_lpips_pack')      # (inline, not _enqueue: the message keeps the name it had before the selector)
     return packed
 
 
@@ -1593,10 +1509,8 @@ def lpips_sums(gt: Tensor, image: Tensor, packed: Tensor, mask: Optional[Tensor]
     sums = torch.empty((5,), dtype=torch.float64, device=gt.device)
     taps = [torch.empty((2, th, tw, c), dtype=torch.float32, device=gt.device) for th, tw, c in lpips_tap_shapes(h, w, net)] if return_taps else None
     with torch.cuda.device(gt.device):
-        ws = _lpips_workspaces.get((gt.device, net))
-        if ws is None or ws.numel() < need:
-            ws = _lpips_workspaces[(gt.device, net)] = torch.empty((need,), dtype=torch.uint8, device=gt.device)
+        ws = _workspace(('lpips', net), gt.device, need)      # one per (device, network)
         st = lib.snerf_lpips_net_sums(selector, _ptr(gt), _ptr(image), _ptr(mask), h, w, _ptr(packed), _ptr(sums),
                                       None if taps is None else _pointer_array(taps), _ptr(ws), _stream())
-    _lib.check(st, 'snerf_lpips_sums')
+    _lib.check(st, 'snerf_lpips_sums')      # (as in lpips_pack)
     return (sums, taps) if return_taps else sums

@@ -6,15 +6,17 @@ scaled to 4096 rows) through the C ABI of a given library build: HIP events arou
 
 ``old`` = struct snerf_loss_term of ABI 9 (no d_target tail), ``new`` = ABI 10.  A TAG ending in ``+01`` (new only) times the
 table of all thirteen losses instead: 16 terms, three of them two-sided."""
-import ctypes, json, statistics, sys
+import ctypes, json, os, statistics, sys
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+from simplenerf_amd import _lib  # noqa: E402
+
 lib_path, layout, tag, out_path = sys.argv[1:5]
-c_void_p, c_int, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-fields = [('pred', c_void_p), ('target', c_void_p), ('numerator_mask', c_void_p), ('denominator_mask', c_void_p),
-          ('d_pred', c_void_p), ('channels', c_int), ('group', c_int), ('accumulate', c_int), ('weight', c_float)]
-if layout == 'new':
-    fields += [('d_target', c_void_p), ('accumulate_target', c_int)]
+c_void_p, c_int = ctypes.c_void_p, ctypes.c_int
+fields = list(_lib.LossTerm._fields_)      # struct snerf_loss_term as the header in the tree has it
+if layout == 'old':
+    fields = fields[:[name for name, _ in fields].index('d_target')]      # ABI 9: before the d_target tail was appended
 
 
 class Term(ctypes.Structure):
