@@ -35,12 +35,12 @@ enum snerf_status {
 #define SNERF_ABI_VERSION 10
 /* Threads (no ABI change): every entry point may be called from several host threads at once -- on different devices, on
  * different streams of one device, and on the SAME stream (torch.nn.DataParallel with a repeated device id runs its replicas in
- * parallel threads that enqueue on one stream).  The host-side state the library keeps is guarded: the side streams and fork /
- * join events of the render calls and the layered path's inference scratch block are per (device, stream), and a render call
- * (snerf_render_forward / _backward) or a layered-shape snerf_mlp_forward holds a per-(device, stream) lock from its first launch
- * to its join, so two calls on one stream enqueue one after the other, never interleaved; the packed-format registry, the
- * timing table and the range table sit behind mutexes; kernel attributes are raised once per device with atomic flags; the
- * error message is thread-local.  What the caller owns stays the caller's: two threads must not write the same output or
+ * parallel threads that enqueue on one stream).  The host-side state the library keeps is guarded: ONE table holds one state per
+ * (device, stream) -- its enqueue lock, the side streams and fork / join events of the render calls, the layered path's inference
+ * scratch blocks -- and a render call (snerf_render_forward / _backward) or a layered-shape snerf_mlp_forward holds that lock from
+ * its first launch to its join, so two calls on one stream enqueue one after the other, never interleaved, and nothing else in
+ * the state needs a lock of its own; the packed-format registry, the timing table and the range table sit behind mutexes; kernel
+ * attributes and the CU count are settled once per device with atomic flags; the error message is thread-local.  What the caller owns stays the caller's: two threads must not write the same output or
  * workspace buffers, or re-pack a weight buffer another thread's call still reads.  The fp16 range flag is one per DEVICE:
  * the next fp16-mode call on that device reports it, from whichever thread. */
 int snerf_abi_version(void);

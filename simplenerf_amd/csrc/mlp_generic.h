@@ -54,8 +54,8 @@ int generic_backward_bf16(const GenericPlan& p, const float* packed, const float
                           const float* d_sigma, const float* d_rgb, long long total, float* workspace, float* const* grads,
                           int accumulate, hipStream_t stream);
 
-// scratch of the inference forward (mlp_generic.hip): a block of at least `floats` for the current device and this stream
-int generic_arena(size_t floats, hipStream_t stream, float** out);
+// scratch of the inference forward (host_state.hip): a block of at least `floats` of the (device, stream) whose lock the caller holds
+int generic_arena(const StreamLock& held, size_t floats, float** out);
 
 // row chunks the weight-gradient products of the backward are split into (fixed-order reduction)
 inline int generic_wgrad_splits(long long total) { return (int)std::min<long long>(64, std::max<long long>(1, total / 8192)); }

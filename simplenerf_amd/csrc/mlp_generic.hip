@@ -20,10 +20,9 @@
 // The layer walk -- which layer reads and writes which columns with which parameters, forward and backward -- is written once
 // (mlp_generic_walk.h) for two operand formats: this file is the fp32 one (its GEMMs, its row) together with the plan, the entry
 // points and their precision gate; mlp_generic_bf16.hip is the bf16 one; the fp16 modes are refused for these shapes.  The
-// inference entry point has no workspace argument in the ABI, so this path keeps a per-device scratch arena for it (allocated on
-// first use, grown when needed: a FIRST generic inference call inside a graph capture fails with SNERF_E_HIP).
+// inference entry point has no workspace argument in the ABI, so the library keeps scratch blocks per (device, stream) for it
+// (host_state.hip generic_arena: allocated on first use, grown when needed -- not inside a graph capture).
 #include <algorithm>
-#include <mutex>
 #include <vector>
 
 #include "mlp_device.h"
@@ -510,7 +509,7 @@ int launch_gemm(const GemmArgs& g, int splits, hipStream_t s) {
         const bool b_along_n = g.b_cs == 1 && g.b_rs % 4 == 0 && aligned16(g.B) && g.N % 4 == 0;
         // (persistent workgroups: two per CU of the current device, a multiple of eight so that a workgroup's tiles stay on its XCD)
         const unsigned tiles = grid.x * grid.y;
-        const dim3 walkers(tiles < persistent_workgroups() ? tiles : persistent_workgroups(), 1, grid.z);
+        const dim3 walkers(std::min(tiles, snerf::persistent_workgroups()), 1, grid.z);
         if (a_along_k && b_along_k) hipLaunchKernelGGL((gemm_vec_kernel<128, 128, 1, 1>), walkers, dim3(256), 0, s, g);
         else if (a_along_k && b_along_n) hipLaunchKernelGGL((gemm_vec_kernel<128, 128, 1, 2>), walkers, dim3(256), 0, s, g);
         else if (a_along_m && b_along_n) hipLaunchKernelGGL((gemm_vec_kernel<128, 128, 2, 2>), walkers, dim3(256), 0, s, g);
@@ -569,16 +568,6 @@ struct F32Operands {
     }
 };
 
-// Scratch of the inference entry point (the ABI gives it no workspace argument): one block per (device, stream), so that two
-// layered-shape forwards on different streams of a device do not share an activation matrix (they used to); two
-// threads on ONE stream take turns (the call holds the stream's StreamLock over all of its passes).  A block is NEVER freed or moved once handed out -- an in-flight kernel or a captured graph may hold its address; a
-// larger request on the same stream allocates another block and the old one stays (sizes are bounded by kInferenceChunk rows,
-// so a stream grows its block a handful of times at most).  Growing inside a graph capture is refused: the allocation would be
-// a synchronous call the capture cannot contain.
-struct ArenaBlock { int device; hipStream_t stream; float* base; size_t floats; };
-std::mutex g_arena_mutex;
-std::vector<ArenaBlock> g_arena;
-
 // fp32 or bf16 operands ('bf16s8' is 'bf16' here: the fp8 saved trunk exists for the fused 256-wide kernels only): *bf16 says which.
 // The fp16 modes are refused for these shapes, not run in another precision.
 int layered_operands(const GenericPlan& p, int precision, const char* entry, bool* bf16) {
@@ -592,32 +581,6 @@ int layered_operands(const GenericPlan& p, int precision, const char* entry, boo
 }  // namespace
 
 namespace snerf {
-
-int generic_arena(size_t floats, hipStream_t stream, float** out) {
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return fail(SNERF_E_HIP, "mlp_forward(layered): no current HIP device");
-    std::lock_guard<std::mutex> lock(g_arena_mutex);
-    for (const ArenaBlock& b : g_arena)
-        if (b.device == device && b.stream == stream && b.floats >= floats) {
-            *out = b.base;
-            return SNERF_OK;
-        }
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &capturing) == hipSuccess && capturing != hipStreamCaptureStatusNone)
-        return fail(SNERF_E_UNSUPPORTED, "mlp_forward(layered): the scratch block of this stream must grow to %zu MB, which a graph "
-                                         "capture cannot contain -- run one call of this size on the stream before capturing",
-                    floats * sizeof(float) >> 20);
-    (void)hipGetLastError();
-    void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, floats * sizeof(float));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(SNERF_E_HIP, "mlp_forward(layered): scratch of %zu MB: %s", floats * sizeof(float) >> 20, hipGetErrorString(e));
-    }
-    g_arena.push_back({device, stream, static_cast<float*>(p), floats});
-    *out = static_cast<float*>(p);
-    return SNERF_OK;
-}
 
 int generic_plan(const snerf_mlp_desc* d, GenericPlan* out) {
     if (!d) return fail(SNERF_E_INVALID, "mlp: NULL descriptor");

@@ -130,16 +130,4 @@ __global__ void __launch_bounds__(256) colsum_kernel(const float* __restrict__ d
     if (part == 0 && col < cols) partial[(long long)blockIdx.y * cols + col] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
 }
 
-// two workgroups per CU of the current device, rounded down to a multiple of eight (512 on an MI355X)
-inline unsigned persistent_workgroups() {
-    int device = 0, cus = 256;
-    if (hipGetDevice(&device) == hipSuccess) {
-        int value = 0;
-        if (hipDeviceGetAttribute(&value, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && value > 0) cus = value;
-    }
-    (void)hipGetLastError();
-    const unsigned count = (unsigned)(2 * cus) & ~7u;
-    return count ? count : 8u;
-}
-
 }  // namespace

@@ -110,7 +110,7 @@ int forward_call(const GenericPlan& p, const float* packed, const float* origins
     // every pass of the call writes and reads the stream's one scratch block: no other thread's pass may come in between
     const snerf::StreamLock serialised(s);
     float* scratch = nullptr;
-    const int rc = snerf::generic_arena((size_t)std::min(num_rays, rays_per_chunk) * num_samples * p.row, s, &scratch);
+    const int rc = snerf::generic_arena(serialised, (size_t)std::min(num_rays, rays_per_chunk) * num_samples * p.row, &scratch);
     if (rc != SNERF_OK) return rc;
     for (long long ray = 0; ray < num_rays; ray += rays_per_chunk) {
         const long long rays = std::min(rays_per_chunk, num_rays - ray);

@@ -3,9 +3,6 @@
 // instead of one per stage.  Orchestration only: every stage is one of the library's own entry points (K2 depths.hip,
 // K3 mlp_forward*.hip, K4/K6 composite.hip, K5 depths.hip, K7 mlp_backward*.hip).
 #include <algorithm>
-#include <map>
-#include <mutex>
-#include <utility>
 
 #include "render_layout.h"
 #include "snerf_common.h"
@@ -37,66 +34,56 @@ struct Marching {
 // augmentation levels run on side streams beside the main levels (forward: {main coarse -> fine} | points-aug | views-aug;
 // backward: all four side by side), forked from and joined to the caller's stream with events -- still enqueue-only, and a
 // capture of the caller's stream captures the side streams with it (fork / join is what a HIP graph records as parallel
-// branches).  Side streams and events are created once per (device, caller's stream) and kept; a call holds its stream's
-// StreamLock from the first launch to the join, so two host threads rendering on one stream never share a fork or join event
-// between their calls.  Above the threshold every CU is
+// branches).  The side streams and events belong to the caller's (device, stream) state (snerf_common.h side_streams); a call
+// holds its stream's StreamLock from the first launch to the join, so two host threads rendering on one stream never share a
+// fork or join event between their calls.  Above the threshold every CU is
 // busy with one level and the levels stay on the caller's stream, in order (two backward calls side by side measured the same
 // as back to back there: DESIGN_LOG 12.4).
 constexpr long long kSideBySideSamples = 65536;
-constexpr int kSideStreams = 3;
+using snerf::kSideStreams;
 
-struct SideStreams {
-    hipStream_t stream[kSideStreams] = {};
-    hipEvent_t fork = nullptr, join[kSideStreams] = {};
-    bool ok = false;
-};
-std::mutex g_side_mutex;
-std::map<std::pair<int, hipStream_t>, SideStreams> g_side;
+// One call's fork of the side streams from the caller's stream and their join back to it.  Built from the StreamLock the call holds;
+// false when the call keeps its levels in order (not `wanted`, or no side streams to be had).  From begin() on every way out of the
+// scope joins what was forked: finish(), or the destructor for a return that did not go through it.
+class ForkScope {
+public:
+    ForkScope(const snerf::StreamLock& held, hipStream_t main, bool wanted) : main_(main), side_(wanted ? snerf::side_streams(held) : nullptr) {}
+    ~ForkScope() { (void)join(); }
+    ForkScope(const ForkScope&) = delete;
+    ForkScope& operator=(const ForkScope&) = delete;
+    explicit operator bool() const { return side_ != nullptr; }
+    snerf_stream_t stream(int i) const { return (snerf_stream_t)side_->stream[i]; }
 
-SideStreams* side_streams(hipStream_t main) {
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lock(g_side_mutex);
-    // (streams and events are kept for the life of the process -- a captured graph may hold them; a caller that keeps creating
-    // streams gets side streams for the first kMaxSideSets of them and plain in-order levels afterwards)
-    constexpr size_t kMaxSideSets = 64;
-    auto found = g_side.find({device, main});
-    if (found == g_side.end() && g_side.size() >= kMaxSideSets) return nullptr;
-    SideStreams& s = g_side[{device, main}];
-    if (!s.ok) {
-        bool good = hipEventCreateWithFlags(&s.fork, hipEventDisableTiming) == hipSuccess;
-        for (int i = 0; i < kSideStreams && good; ++i)
-            good = hipStreamCreateWithFlags(&s.stream[i], hipStreamNonBlocking) == hipSuccess &&
-                   hipEventCreateWithFlags(&s.join[i], hipEventDisableTiming) == hipSuccess;
-        if (!good) {                 // (the caller falls back to one stream; nothing half-made stays behind)
-            (void)hipGetLastError();
-            if (s.fork) (void)hipEventDestroy(s.fork);
-            for (int i = 0; i < kSideStreams; ++i) {
-                if (s.join[i]) (void)hipEventDestroy(s.join[i]);
-                if (s.stream[i]) (void)hipStreamDestroy(s.stream[i]);
-            }
-            g_side.erase({device, main});
-            return nullptr;
+    // the first `count` side streams wait for what the caller's stream holds so far; a failure part-way joins those that already wait
+    int begin(int count) {
+        if (hipEventRecord(side_->fork, main_) != hipSuccess) return snerf::fail(SNERF_E_HIP, "render: hipEventRecord(fork) failed");
+        for (int i = 0; i < count; ++i) {
+            if (hipStreamWaitEvent(side_->stream[i], side_->fork, 0) == hipSuccess) { forked_ = i + 1; continue; }
+            (void)join();
+            return snerf::fail(SNERF_E_HIP, "render: hipStreamWaitEvent(fork) failed");
         }
-        s.ok = true;
+        return SNERF_OK;
     }
-    return &s;
-}
+    // the caller's stream waits for the forked streams; -> `status`, or the join's failure if `status` was OK
+    int finish(int status) {
+        const int joined = join();
+        return status != SNERF_OK ? status : joined;
+    }
 
-// fork: the side streams wait for what the caller's stream holds so far; join: the caller's stream waits for them
-int fork_streams(SideStreams* s, hipStream_t main, int count) {
-    if (hipEventRecord(s->fork, main) != hipSuccess) return snerf::fail(SNERF_E_HIP, "render: hipEventRecord(fork) failed");
-    for (int i = 0; i < count; ++i)
-        if (hipStreamWaitEvent(s->stream[i], s->fork, 0) != hipSuccess) return snerf::fail(SNERF_E_HIP, "render: hipStreamWaitEvent(fork) failed");
-    return SNERF_OK;
-}
-int join_streams(SideStreams* s, hipStream_t main, int count) {
-    for (int i = 0; i < count; ++i) {
-        if (hipEventRecord(s->join[i], s->stream[i]) != hipSuccess) return snerf::fail(SNERF_E_HIP, "render: hipEventRecord(join) failed");
-        if (hipStreamWaitEvent(main, s->join[i], 0) != hipSuccess) return snerf::fail(SNERF_E_HIP, "render: hipStreamWaitEvent(join) failed");
+private:
+    int join() {
+        int rc = SNERF_OK;
+        for (int i = 0; i < forked_; ++i) {      // (a stream that cannot be joined does not keep the others from being joined)
+            if (hipEventRecord(side_->join[i], side_->stream[i]) != hipSuccess) rc = snerf::fail(SNERF_E_HIP, "render: hipEventRecord(join) failed");
+            else if (hipStreamWaitEvent(main_, side_->join[i], 0) != hipSuccess) rc = snerf::fail(SNERF_E_HIP, "render: hipStreamWaitEvent(join) failed");
+        }
+        forked_ = 0;
+        return rc;
     }
-    return SNERF_OK;
-}
+    hipStream_t main_;
+    snerf::SideStreams* side_;
+    int forked_ = 0;
+};
 
 bool side_by_side(const snerf_render_config* cfg, const snerf_render_mlp* mlps, long long num_rays) {
     if (num_rays * cfg->num_coarse > kSideBySideSamples) return false;
@@ -240,57 +227,61 @@ extern "C" int snerf_render_forward(const snerf_render_config* cfg, const snerf_
     rc = snerf_coarse_depths(rays->near, rays->far, n, cfg->num_coarse, cfg->lindisp, rays->t_rand, out->depths_coarse, stream);
     if (rc != SNERF_OK) return rc;
     // the coarse augmentation levels beside {main coarse -> fine} when the call is small (see side_by_side)
-    SideStreams* side = side_by_side(cfg, mlps, n) && (mlps[1].desc || mlps[2].desc) ? side_streams((hipStream_t)stream) : nullptr;
-    int forked = 0;
-    // (from the fork on every return joins the side streams first)
-    auto done = [&](int status) { return side ? (join_streams(side, (hipStream_t)stream, forked) == SNERF_OK ? status : (status != SNERF_OK ? status : SNERF_E_HIP)) : status; };
+    ForkScope side(serialised, (hipStream_t)stream, side_by_side(cfg, mlps, n) && (mlps[1].desc || mlps[2].desc));
     if (side) {
-        forked = (mlps[1].desc ? 1 : 0) + (mlps[2].desc ? 1 : 0);
-        rc = fork_streams(side, (hipStream_t)stream, forked);
+        rc = side.begin((mlps[1].desc ? 1 : 0) + (mlps[2].desc ? 1 : 0));
         if (rc != SNERF_OK) return rc;
     }
     // the main coarse level FIRST: the fine level waits for it, so its workgroups must not queue behind the augmentation levels'
     // (enqueued last it ran last: 140 us instead of 86 and the fine pass started that much later, r05 trace of a 512-row pass)
     rc = shade(0, out->depths_coarse, cfg->num_coarse, stream);
-    if (rc != SNERF_OK) return done(rc);
+    if (rc != SNERF_OK) return side.finish(rc);
     int used = 0;
     for (int l = 1; l < 3; ++l) {
         if (!mlps[l].desc) continue;
-        rc = shade(l, out->depths_coarse, cfg->num_coarse, side ? (snerf_stream_t)side->stream[used++] : stream);
-        if (rc != SNERF_OK) return done(rc);
+        rc = shade(l, out->depths_coarse, cfg->num_coarse, side ? side.stream(used++) : stream);
+        if (rc != SNERF_OK) return side.finish(rc);
     }
-    if (!fine) return done(SNERF_OK);
+    if (!fine) return side.finish(SNERF_OK);
     const float* depths_fine = rays->depths_fine;
     if (!depths_fine) {
         if (!fuse_resample) {     // (else the main coarse level's kernel has written them already)
             rc = snerf_resample_depths(out->depths_coarse, coarse_weights, n, cfg->num_coarse, cfg->num_fine, rays->u,
                                        out->depths_fine, stream);
-            if (rc != SNERF_OK) return done(rc);
+            if (rc != SNERF_OK) return side.finish(rc);
         }
         depths_fine = out->depths_fine;
     }
     for (int l = 3; l < SNERF_RENDER_LEVELS; ++l) {
         if (!mlps[l].desc) continue;
         rc = shade(l, depths_fine, snerf::renderlayout::samples(cfg, l), stream);
-        if (rc != SNERF_OK) return done(rc);
+        if (rc != SNERF_OK) return side.finish(rc);
     }
-    return done(SNERF_OK);
+    return side.finish(SNERF_OK);
 }
+
+namespace {
+// The backward workspace of a call (renderlayout::backward_regions).  `with_inner`: ask every present level's MLP backward for its
+// inner workspace -- what the total and the side-by-side offsets depend on; the in-order offsets do not.
+snerf::renderlayout::BackwardRegions backward_regions(const snerf_render_config* cfg, const snerf_render_mlp* mlps, long long n,
+                                                      bool side_by_side, bool with_inner) {
+    int samples[SNERF_RENDER_LEVELS];
+    bool present[SNERF_RENDER_LEVELS];
+    size_t inner[SNERF_RENDER_LEVELS] = {};
+    for (int l = 0; l < SNERF_RENDER_LEVELS; ++l) {
+        samples[l] = snerf::renderlayout::samples(cfg, l);
+        present[l] = mlps[l].desc != nullptr;
+        if (present[l] && with_inner) inner[l] = snerf_mlp_backward_workspace_floats(mlps[l].desc, n, samples[l]);
+    }
+    return snerf::renderlayout::backward_regions(samples, present, inner, n, side_by_side);
+}
+}  // namespace
 
 extern "C" size_t snerf_render_backward_workspace_floats(const snerf_render_config* cfg, const snerf_render_mlp* mlps,
                                                          long long num_rays) {
     if (!cfg || !mlps || num_rays < 0 || cfg->num_coarse < 1 || cfg->num_fine < 0) return 0;
-    size_t samples = 0, inner = 0, every = 0;
-    for (int l = 0; l < SNERF_RENDER_LEVELS; ++l) {
-        if (!mlps[l].desc) continue;
-        const int s = snerf::renderlayout::samples(cfg, l);
-        const size_t level_inner = snerf_mlp_backward_workspace_floats(mlps[l].desc, num_rays, s);
-        samples = std::max(samples, (size_t)num_rays * (size_t)s);
-        inner = std::max(inner, level_inner);
-        every += 4 * (size_t)num_rays * (size_t)s + (level_inner + 63) / 64 * 64;
-    }
     // levels side by side (small calls): each level its own gradient columns and inner workspace
-    return side_by_side(cfg, mlps, num_rays) ? every : 4 * samples + inner;
+    return backward_regions(cfg, mlps, num_rays, side_by_side(cfg, mlps, num_rays), true).total;
 }
 
 extern "C" int snerf_render_backward(const snerf_render_config* cfg, const snerf_render_mlp* mlps, const snerf_render_rays* rays,
@@ -304,11 +295,18 @@ extern "C" int snerf_render_backward(const snerf_render_config* cfg, const snerf
     const long long n = num_rays;
     const snerf::StreamLock serialised((hipStream_t)stream);
     const float* march_d = cfg->ndc ? rays->rays_d_ndc : rays->rays_d;
-    size_t samples_max = 0;
-    for (int l = 0; l < SNERF_RENDER_LEVELS; ++l)
-        if (mlps[l].desc) samples_max = std::max(samples_max, (size_t)n * (size_t)snerf::renderlayout::samples(cfg, l));
-    // one level's backward on `s`: compositing backward (K6) -> raw-output gradients added -> MLP backward (K7)
-    auto level_backward = [&](int l, float* d_sigma, float* d_rgb, float* inner, snerf_stream_t s_l) -> int {
+    auto wanted = [&](int l) {
+        const snerf_render_level_grads& g = grads[l];
+        return mlps[l].desc && g.param_grads && (g.rgb || g.acc || g.depth || g.depth_ndc || g.sigma || g.raw_rgb);
+    };
+    int levels = 0;
+    for (int l = 0; l < SNERF_RENDER_LEVELS; ++l) levels += wanted(l) ? 1 : 0;
+    ForkScope side(serialised, (hipStream_t)stream, side_by_side(cfg, mlps, n) && levels > 1);
+    // side by side each level has its own region of the workspace; in order they share one
+    const snerf::renderlayout::BackwardRegions at = backward_regions(cfg, mlps, n, (bool)side, (bool)side);
+    // one level's backward on `s_l`: compositing backward (K6) -> raw-output gradients added -> MLP backward (K7)
+    auto level_backward = [&](int l, snerf_stream_t s_l) -> int {
+        float *d_sigma = workspace + at.d_sigma[l], *d_rgb = workspace + at.d_rgb[l], *inner = workspace + at.inner[l];
         const snerf_render_level_grads& g = grads[l];
         const int s = snerf::renderlayout::samples(cfg, l);
         const float* depths = l < 3 ? out->depths_coarse : (rays->depths_fine ? rays->depths_fine : out->depths_fine);
@@ -330,52 +328,30 @@ extern "C" int snerf_render_backward(const snerf_render_config* cfg, const snerf
         return snerf_mlp_backward(mlps[l].desc, mlps[l].packed, o.saved_acts, o.sigma, o.raw_rgb, d_sigma, d_rgb, n, s, inner,
                                   g.param_grads, g.num_params, cfg->precision, g.accumulate, s_l);
     };
-    auto wanted = [&](int l) {
-        const snerf_render_level_grads& g = grads[l];
-        return mlps[l].desc && g.param_grads && (g.rgb || g.acc || g.depth || g.depth_ndc || g.sigma || g.raw_rgb);
-    };
-    int levels = 0;
-    for (int l = 0; l < SNERF_RENDER_LEVELS; ++l) levels += wanted(l) ? 1 : 0;
-    SideStreams* side = side_by_side(cfg, mlps, n) && levels > 1 ? side_streams((hipStream_t)stream) : nullptr;
     if (!side) {
-        float* d_sigma = workspace;
-        float* d_rgb = workspace + samples_max;
-        float* inner = workspace + 4 * samples_max;
         for (int l = 0; l < SNERF_RENDER_LEVELS; ++l) {
             if (!wanted(l)) continue;
-            rc = level_backward(l, d_sigma, d_rgb, inner, stream);
+            rc = level_backward(l, stream);
             if (rc != SNERF_OK) return rc;
         }
         return SNERF_OK;
     }
     // side by side: the heaviest level (main fine, else the first wanted) stays on the caller's stream, the others take the side
-    // streams in turn; each level has its own region of the workspace (snerf_render_backward_workspace_floats)
+    // streams in turn
     const int forked = std::min(levels - 1, kSideStreams);
-    rc = fork_streams(side, (hipStream_t)stream, forked);
+    rc = side.begin(forked);
     if (rc != SNERF_OK) return rc;
     int keep = wanted(SNERF_LEVEL_MAIN_FINE) ? SNERF_LEVEL_MAIN_FINE : -1;
     for (int l = 0; keep < 0 && l < SNERF_RENDER_LEVELS; ++l)
         if (wanted(l)) keep = l;
-    // each level's region of the workspace, in level order
-    float* d_sigma_of[SNERF_RENDER_LEVELS] = {};
-    float* region = workspace;
-    size_t samples_of[SNERF_RENDER_LEVELS] = {};
-    for (int l = 0; l < SNERF_RENDER_LEVELS; ++l) {
-        if (!mlps[l].desc) continue;
-        const int s_l = snerf::renderlayout::samples(cfg, l);
-        samples_of[l] = (size_t)n * (size_t)s_l;
-        d_sigma_of[l] = region;
-        region += 4 * samples_of[l] + (snerf_mlp_backward_workspace_floats(mlps[l].desc, n, s_l) + 63) / 64 * 64;
-    }
     // the kept (heaviest) level is enqueued first -- enqueued last, its kernels queued behind everybody else's and the call ended
     // with it -- then the others, each on its side stream
     int used = 0;
-    rc = level_backward(keep, d_sigma_of[keep], d_sigma_of[keep] + samples_of[keep], d_sigma_of[keep] + 4 * samples_of[keep], stream);
+    rc = level_backward(keep, stream);
     for (int l = 0; l < SNERF_RENDER_LEVELS && rc == SNERF_OK; ++l) {
         if (!wanted(l) || l == keep) continue;
-        rc = level_backward(l, d_sigma_of[l], d_sigma_of[l] + samples_of[l], d_sigma_of[l] + 4 * samples_of[l],
-                            (snerf_stream_t)side->stream[used++ % forked]);
+        rc = level_backward(l, side.stream(used++ % forked));
     }
-    const int joined = join_streams(side, (hipStream_t)stream, forked);
-    return rc != SNERF_OK ? rc : joined;
+    return side.finish(rc);
 }
+

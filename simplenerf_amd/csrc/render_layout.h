@@ -8,6 +8,7 @@
 // depth, depth_var, [depth_ndc, depth_var_ndc], [visibility2].
 #pragma once
 
+#include <cstddef>
 #include <initializer_list>
 
 #include "simplenerf_hip.h"
@@ -98,6 +99,44 @@ inline void bind(const snerf_render_layout* lay, long long n, float* per_ray_poo
     out->depths_fine = at(lay->depths_fine);
     for (int l = 0; l < SNERF_RENDER_LEVELS; ++l)
         for (int f = 0; f < SNERF_RENDER_FIELDS; ++f) out->level[l].*kField[f] = at(lay->level[l][f]);
+}
+
+// The workspace of snerf_render_backward, in floats: per level the gradient columns d_sigma (n s_l) and d_rgb (3 n s_l) and the
+// inner workspace of the level's MLP backward.  The ONE place that knows the partition: snerf_render_backward_workspace_floats
+// sizes the allocation with it, snerf_render_backward carves it.
+//   in order (the levels run one after the other and share one region): [ d_sigma | d_rgb | inner ] sized for the largest level,
+//       4 max_l(n s_l) + max_l(inner_l);
+//   side by side (each present level its own region, in level order): 4 n s_l + round_up(inner_l, 64) per level.
+// A call sized side by side but run in order (one level wanted, no side streams to be had) carves the in-order offsets, which
+// depend on the sample counts only, out of the larger allocation.
+struct BackwardRegions {
+    size_t d_sigma[SNERF_RENDER_LEVELS], d_rgb[SNERF_RENDER_LEVELS], inner[SNERF_RENDER_LEVELS];   // offsets; 0 for absent levels
+    size_t total;
+};
+
+inline BackwardRegions backward_regions(const int (&samples)[SNERF_RENDER_LEVELS], const bool (&present)[SNERF_RENDER_LEVELS],
+                                        const size_t (&inner_floats)[SNERF_RENDER_LEVELS], long long n, bool side_by_side) {
+    BackwardRegions r = {};
+    size_t columns_max = 0, inner_max = 0;
+    for (int l = 0; l < SNERF_RENDER_LEVELS; ++l) {
+        if (!present[l]) continue;
+        const size_t columns = (size_t)n * (size_t)samples[l];
+        if (columns > columns_max) columns_max = columns;
+        if (inner_floats[l] > inner_max) inner_max = inner_floats[l];
+        if (!side_by_side) continue;
+        r.d_sigma[l] = r.total;
+        r.d_rgb[l] = r.total + columns;
+        r.inner[l] = r.total + 4 * columns;
+        r.total += 4 * columns + (inner_floats[l] + 63) / 64 * 64;
+    }
+    if (side_by_side) return r;
+    for (int l = 0; l < SNERF_RENDER_LEVELS; ++l) {
+        if (!present[l]) continue;
+        r.d_rgb[l] = columns_max;
+        r.inner[l] = 4 * columns_max;
+    }
+    r.total = 4 * columns_max + inner_max;
+    return r;
 }
 
 }  // namespace renderlayout

@@ -199,8 +199,77 @@ static int check_refusals() {
     return 0;
 }
 
+// backward_regions: the workspace partition of snerf_render_backward.  Over n x sample counts x every level set the render entry
+// points admit (main coarse always; fine levels only with num_fine > 0 and the main fine level) x inner sizes around the 64-float
+// rounding: the totals equal the two formulas written out here, the regions are disjoint and in level order, every level's columns
+// and inner workspace fit its region, and the in-order layout fits inside what a side-by-side call allocates.
+static int check_backward_regions() {
+    const size_t inner_sizes[5] = {0, 1, 63, 64, 65};
+    const int counts[3][2] = {{1, 0}, {3, 2}, {64, 64}};
+    long long cases = 0;
+    for (long long n : {0LL, 1LL, 7LL, 512LL})
+        for (const auto& count : counts)
+            for (int set = 0; set < 32; ++set)
+                for (int shift = 0; shift < 5; ++shift) {
+                    bool present[SNERF_RENDER_LEVELS] = {true};
+                    for (int l = 1; l < SNERF_RENDER_LEVELS; ++l) present[l] = (set >> (l - 1)) & 1;
+                    const bool fine = present[3] || present[4] || present[5];
+                    if (fine && (count[1] == 0 || !present[3])) continue;
+                    int s[SNERF_RENDER_LEVELS];
+                    size_t inner[SNERF_RENDER_LEVELS];
+                    for (int l = 0; l < SNERF_RENDER_LEVELS; ++l) {
+                        s[l] = samples(count[0], count[1], l);
+                        CHECK(s[l] == (l < 3 ? count[0] : count[0] + count[1]));
+                        inner[l] = present[l] ? inner_sizes[(l + shift) % 5] : 12345;     // (an absent level's size is not looked at)
+                    }
+                    size_t every = 0, columns_max = 0, inner_max = 0;
+                    for (int l = 0; l < SNERF_RENDER_LEVELS; ++l) {
+                        if (!present[l]) continue;
+                        const size_t columns = (size_t)n * (size_t)s[l];
+                        every += 4 * columns + (inner[l] + 63) / 64 * 64;
+                        columns_max = std::max(columns_max, columns);
+                        inner_max = std::max(inner_max, inner[l]);
+                    }
+                    const BackwardRegions side = backward_regions(s, present, inner, n, true);
+                    const BackwardRegions order = backward_regions(s, present, inner, n, false);
+                    CHECK(side.total == every && order.total == 4 * columns_max + inner_max && order.total <= side.total);
+                    size_t at = 0;
+                    for (int l = 0; l < SNERF_RENDER_LEVELS; ++l) {
+                        if (!present[l]) {
+                            CHECK(side.d_sigma[l] == 0 && side.d_rgb[l] == 0 && side.inner[l] == 0);
+                            CHECK(order.d_sigma[l] == 0 && order.d_rgb[l] == 0 && order.inner[l] == 0);
+                            continue;
+                        }
+                        const size_t columns = (size_t)n * (size_t)s[l];
+                        // side by side: [ d_sigma | d_rgb | inner ] from where the level before ended, the next one a multiple of 64 on
+                        CHECK(side.d_sigma[l] == at && side.d_rgb[l] == at + columns && side.inner[l] == at + 4 * columns);
+                        const size_t end = side.inner[l] + inner[l];
+                        at = side.inner[l] + (inner[l] + 63) / 64 * 64;
+                        CHECK(end <= at && at - end < 64 && (at - side.d_sigma[l] - 4 * columns) % 64 == 0 && at <= side.total);
+                        // in order: one shared region sized for the largest level
+                        CHECK(order.d_sigma[l] == 0 && order.d_rgb[l] == columns_max && order.inner[l] == 4 * columns_max);
+                        CHECK(columns <= order.d_rgb[l] && order.d_rgb[l] + 3 * columns <= order.inner[l] && order.inner[l] + inner[l] <= order.total);
+                    }
+                    CHECK(at == side.total);
+                    ++cases;
+                }
+    // level sets: {0} x {1, 2 free} = 4 without a fine pass; with num_fine > 0 also {3} x {4, 5 free} = 4 x 4 more
+    CHECK(cases == 4 * 5 * (4 + 20 + 20));
+    // one layout by hand: levels {0, 3}, 7 rays, 3 + 2 samples, inner 65 and 1
+    {
+        const int s[SNERF_RENDER_LEVELS] = {3, 3, 3, 5, 5, 5};
+        const bool present[SNERF_RENDER_LEVELS] = {true, false, false, true, false, false};
+        const size_t inner[SNERF_RENDER_LEVELS] = {65, 0, 0, 1, 0, 0};
+        const BackwardRegions side = backward_regions(s, present, inner, 7, true), order = backward_regions(s, present, inner, 7, false);
+        CHECK(side.d_sigma[0] == 0 && side.d_rgb[0] == 21 && side.inner[0] == 84 && side.d_sigma[3] == 212 && side.d_rgb[3] == 247 &&
+              side.inner[3] == 352 && side.total == 416);
+        CHECK(order.d_rgb[0] == 35 && order.d_rgb[3] == 35 && order.inner[0] == 140 && order.inner[3] == 140 && order.total == 205);
+    }
+    return 0;
+}
+
 int main() {
-    if (check_sweep() || check_pinned() || check_refusals()) return 1;
+    if (check_sweep() || check_pinned() || check_refusals() || check_backward_regions()) return 1;
     std::printf("render_layout_test: OK\n");
     return 0;
 }

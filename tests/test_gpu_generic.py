@@ -144,6 +144,48 @@ def test_layered_gradients_of_a_large_call_equal_the_sum_over_its_parts(index):
     assert worst < 1e-5
 
 
+def test_two_threads_on_two_streams_each_grow_their_own_scratch():
+    """The inference forward's scratch belongs to the (device, stream) it runs on: two threads, each on a non-default stream of its
+    own, each with its own layered MLP, run a 5-ray x 37-sample call and then a 9-ray x 64-sample one (the stream's block grows once),
+    five times over; every result is bit-equal to the same call made alone on the default stream."""
+    import threading
+    mlps, calls = [], []
+    for index in (1, 2):
+        cfg, sd, _, _ = case(index)
+        mlp = ops.PackedMlp(cfg, DEV)
+        mlp.pack(synth.abi_param_list({k: torch.from_numpy(a).to(DEV) for k, a in sd.items()}))
+        mlps.append(mlp)
+        calls.append([[t.to(DEV) for t in case(index, n, s)[2]] for n, s in ((5, 37), (9, 64))])
+    alone = [[mlp.forward(*inputs) for inputs in mine] for mlp, mine in zip(mlps, calls)]
+    torch.cuda.synchronize()
+    streams = [torch.cuda.Stream(device=DEV) for _ in range(2)]
+    results, errors = [[], []], []
+    start = threading.Barrier(2)
+
+    def work(i):
+        try:
+            with torch.cuda.stream(streams[i]):
+                assert torch.cuda.current_stream(0) == streams[i] != torch.cuda.default_stream(0)
+                start.wait()
+                for _ in range(5):
+                    results[i].append([mlps[i].forward(*inputs) for inputs in calls[i]])
+        except BaseException as error:       # (reported below, in the test's thread)
+            errors.append(error)
+
+    threads = [threading.Thread(target=work, args=(i,)) for i in range(2)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    torch.cuda.synchronize()
+    assert not errors, errors
+    for i in range(2):
+        assert len(results[i]) == 5
+        for rep, got in enumerate(results[i]):
+            for call, ((sigma, rgb), (want_sigma, want_rgb)) in enumerate(zip(got, alone[i])):
+                assert torch.equal(sigma, want_sigma) and torch.equal(rgb, want_rgb), (i, rep, call)
+
+
 def test_the_fp16_modes_are_refused_for_layered_shapes_not_silently_run_in_fp32():
     cfg, sd, inputs, _ = case(1)
     mlp = ops.PackedMlp(cfg, DEV)
