@@ -420,6 +420,10 @@ int snerf_render_layout_bind(const snerf_render_layout* layout, long long num_ra
 int snerf_to_display(const float* rgb, const float* depth, long long num_rays, unsigned char* image, float* depth_out,
                      snerf_stream_t stream);
 
+/* The trainer's 8-bit previews (rint(x / max(x) * 255) over whole maps; snerf_maps_to_u8) are an entry point of the same library
+ * that is NOT declared in this header: the set of prototypes here is pinned, so it has a header of its own,
+ * simplenerf_amd/csrc/simplenerf_maps.h, which the Python binding reads after this one. */
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Q1  scoring a rendered frame on the device: the sums behind the reference's frame metrics (src/qa/01_RMSE, 02_PSNR,
  * 03_SSIM, 05_DepthRMSE, 06_DepthMAE, 07_DepthSROCC and their masked forms 11-13, 15-17); the host turns them into the

@@ -15,7 +15,7 @@ from .build import INCLUDE
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libsimplenerf_hip.so')
 
-# The two headers are the binding's only source: every prototype, struct layout, #define and enumerator below is read from them
+# The headers are the binding's only source (the two under include/, then ADDED_HEADERS below): every prototype, struct layout, #define and enumerator below is read from them
 # (_cdecl.py), in inclusion order.  snerf_iteration records live in pinned host and device memory and are passed by address.
 HEADERS = ('simplenerf_hip.h', 'simplenerf_train.h')
 _decls = _cdecl.Header(by_address=('snerf_iteration',))
@@ -25,7 +25,14 @@ for _name in HEADERS:
 
 C = types.SimpleNamespace(**_decls.constants)      # C.SNERF_PRECISION_BF16, C.SNERF_E_RANGE, ...
 STRUCTS = _decls.structs                           # typedef name -> ctypes.Structure class
-SIGNATURES = _decls.functions                      # name -> (restype, argtypes)
+SIGNATURES = dict(_decls.functions)                # name -> (restype, argtypes): the prototypes of the two headers under include/
+# Entry points declared beside those headers (their prototypes are a pinned set): read by the same reader, after them, and bound
+# by load() like the rest.
+ADDED_HEADERS = (os.path.join(_HERE, 'csrc', 'simplenerf_maps.h'),)
+for _name in ADDED_HEADERS:
+    with open(_name) as _f:
+        _decls.read(_f.read(), os.path.basename(_name))
+ADDED_SIGNATURES = {_name: _sig for _name, _sig in _decls.functions.items() if _name not in SIGNATURES}
 ABI_VERSION = C.SNERF_ABI_VERSION
 RENDER_LEVELS, CAMERA_FLOATS = C.SNERF_RENDER_LEVELS, C.SNERF_CAMERA_FLOATS
 LOSS_MAX_TERMS, LOSS_MAX_GROUPS = C.SNERF_LOSS_MAX_TERMS, C.SNERF_LOSS_MAX_GROUPS
@@ -52,7 +59,7 @@ def load() -> ctypes.CDLL:
     # device pointers, streams and the primary context are shared with torch's allocator.
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **ADDED_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

@@ -29,5 +29,19 @@ __device__ __forceinline__ T block_sum(T v, T* lds) {
     return s;
 }
 
+// The same walk for any associative, commutative `op` (e.g. a maximum): valid in EVERY thread.
+template <typename T, typename Op>
+__device__ __forceinline__ T block_fold(T v, T* lds, Op op) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    T s = lds[0];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) s = op(s, lds[w]);
+    return s;
+}
+
 }  // namespace reduce
 }  // namespace snerf

@@ -11,6 +11,10 @@ the reference's switch (:35): each (n, 1), the pixel-ray rows gathered from the 
 ``common_data`` = {poses, intrinsics, images (each with a leading per-GPU axis of ``len(configs['device'])``, default 1),
 resolution}.
 
+``mode='validation'`` (default ``'train'``) assembles the batches of a validation-mode preprocessor (:528-543): the loader's sparse-
+and dense-depth sections are ignored, ``common_data`` stays empty, and without an image number the rows are pixel rows of the
+assembler's own views from its own index stream.
+
 ``scene`` is what the reference's preprocessing leaves in ``preprocessed_data_dict``; ``DataPreprocessor01.DataPreprocessor``
 builds it from the loader's raw data (pose recentring on the host, images, sparse-depth rasterisation and NDC depth tables on
 the device) and owns a BatchAssembler.  Dataset loading stays outside this build (out of scope):
@@ -47,13 +51,17 @@ Tensor = torch.Tensor
 
 
 class BatchAssembler:
-    def __init__(self, configs: dict, scene: dict, device='cuda:0', rank: int = 0, world_size: int = 1):
+    def __init__(self, configs: dict, scene: dict, device='cuda:0', rank: int = 0, world_size: int = 1, mode: str = 'train'):
         loader = configs['data_loader']
         self.configs = configs
+        self.mode = mode.lower()
+        if self.mode not in ('train', 'validation'):
+            raise RuntimeError(f"BatchAssembler: mode 'train' or 'validation', got {mode!r}")
+        train = self.mode == 'train'
         self.device = torch.device(device)
         self.ndc = bool(loader['ndc'])
         self.num_rays = int(loader['num_rays'])
-        self.sparse_depth_needed = 'sparse_depth' in loader
+        self.sparse_depth_needed = train and 'sparse_depth' in loader
         self.num_rays_sparse_depth = int(loader['sparse_depth']['num_rays']) if self.sparse_depth_needed else 0
         self.seed = int(configs.get('seed', 0))
         self.rank, self.world_size = int(rank), int(world_size)
@@ -77,7 +85,7 @@ class BatchAssembler:
                 raise RuntimeError("configs['data_loader']['sparse_depth'] is set but the scene has no 'sparse_depths' table")
             # candidates = pixels with a sparse depth (numpy.where(sparse_depths > 0), :441); built once at start-up
             self.sparse_candidates = torch.nonzero(self.sparse['sparse_depths'] > 0).reshape(-1).contiguous()
-        self.dense_depth_needed = 'dense_depth' in loader
+        self.dense_depth_needed = train and 'dense_depth' in loader
         self.dense = {k: (t(scene[k]).reshape(-1) if scene.get(k) is not None else None)
                       for k in ('dense_depths', 'dense_depth_weights', 'dense_depths_ndc')}
         if self.dense_depth_needed:
@@ -183,6 +191,8 @@ class BatchAssembler:
         if self.dense_depth_needed:
             out.update(ops.gather_dense_depth(indices, num_pixel, self.dense['dense_depths'], self.dense['dense_depth_weights'],
                                               self.dense['dense_depths_ndc'] if self.ndc else None))
+        if self.mode != 'train':       # the shared scene goes to training batches and to validation over the training views only (:540-543)
+            return out
         # shared tensors with the leading per-GPU axis of the reference (:545-551): one copy per entry of configs['device'], so
         # that DataParallel's scatter hands one to each replica; an expanded view, not a copy (one device: the plain [None] view)
         copies = self.num_replicas

@@ -19,6 +19,17 @@ No ray cache is built and nothing per pixel is computed on the host.  ``get_next
 owned ``BatchAssembler``'s (``indices=`` / ``indices_sparse=`` replay a given order; ``rank`` / ``world_size`` pass through), and
 ``get_model_configs()`` returns the reference's dictionary (:65-80; JSON-serialisable).
 
+``mode='validation'`` (the held-out views of the reference's trainer, :44-48) takes the loader's dictionary for those views and the
+train-mode preprocessor's ``get_model_configs()``, which it returns unchanged: poses by the test-mode rule with the training scene's
+``translation_scale`` and ``average_pose``, the loader's ``bounds`` times that scale, near / far by the same rules over THOSE bounds
+(:144-159), images on the device, float32 intrinsics -- and no sparse- or dense-depth tables, whatever the loader sections say
+(:92-99: train mode only; ``raw_data_dict`` need not carry them).  Its ``get_next_batch(iter_num, image_num)`` is the reference's
+validation batch: ``common_data`` empty, no sparse, dense or shared-scene entries (:528-543).
+
+Both modes keep a small host-side ``preprocessed_data_dict`` -- ``frame_nums`` and ``nerf_data`` {``resolution``, ``poses``,
+``intrinsics``, ``bounds``, ``near``, ``far`` [, ``near_ndc``, ``far_ndc``], ``average_pose`` [, ``sc``]} -- which with ``mode`` is what
+the reference's ``Trainer.run_validation`` and ``save_sample_images`` read of a preprocessor (src/Trainer01.py:180, :187, :333-334).
+
 ``create_test_data(pose, preprocess_pose=True, intrinsic=None)`` (any mode with model configs) returns the reference's device batch
 (:851-869) for a raw world-to-camera pose: ``rays_o``, ``rays_d``, ``view_dirs``, ``near``, ``far`` [, ``rays_o_ndc``, ``rays_d_ndc``,
 ``near_ndc``, ``far_ndc``], generated on the device (``harness.frame_batch``).  ``retrieve_inference_outputs`` is the harness's.
@@ -185,6 +196,16 @@ def create_model_configs(host: dict, ndc: bool, mode: str = 'train') -> dict:
     return model_configs
 
 
+def host_view(host: dict, ndc: bool) -> dict:
+    """``preprocessed_data_dict`` as far as the reference's trainer reads it (src/Trainer01.py:180, :187, :333-334): the frame numbers
+    and the per-view host values.  Nothing per pixel: images, rays and depth tables live on the device (``scene``)."""
+    names = ['resolution', 'poses', 'intrinsics', 'bounds', 'near', 'far'] + (['near_ndc', 'far_ndc'] if ndc else []) + ['average_pose']
+    nerf = {name: host[name] for name in names}
+    if 'sc' in host:
+        nerf['sc'] = host['sc']
+    return {'frame_nums': host['frame_nums'], 'nerf_data': nerf}
+
+
 # ------------------------------------------------------------------------------------------------------ the class
 class DataPreprocessor:
     def __init__(self, configs: dict, mode: str, raw_data_dict: Optional[dict] = None, model_configs: Optional[dict] = None,
@@ -204,15 +225,20 @@ class DataPreprocessor:
         self.device = torch.device(device)
         self.raw_data_dict = raw_data_dict
         self.model_configs = model_configs
-        self.scene = self.assembler = None
-        if self.mode == 'train':
-            host = prepare_host(configs, raw_data_dict, 'train')
-            self.model_configs = create_model_configs(host, self.ndc, 'train')
+        self.scene = self.assembler = self.preprocessed_data_dict = None
+        if self.mode in ('train', 'validation'):
+            if self.mode == 'train':
+                host = prepare_host(configs, raw_data_dict, 'train')
+                self.model_configs = create_model_configs(host, self.ndc, 'train')
+            else:
+                if model_configs is None:
+                    raise RuntimeError("mode 'validation': needs the train-mode preprocessor's get_model_configs()")
+                # the sparse / dense loader sections are train-mode only (:92-99): no table is built, none need be given
+                self.sparse_depth_needed = self.dense_depth_needed = False
+                host = prepare_host(configs, raw_data_dict, 'validation', model_configs)
             self.scene = self.build_scene(host, raw_data_dict)
-            self.assembler = BatchAssembler(configs, self.scene, device=self.device, rank=rank, world_size=world_size)
-        elif self.mode == 'validation':
-            raise NotImplementedError("mode 'validation': validation batches come from the train-mode preprocessor "
-                                      "(get_next_batch(iter_num, image_num)), as in the reference's trainer")
+            self.assembler = BatchAssembler(configs, self.scene, device=self.device, rank=rank, world_size=world_size, mode=self.mode)
+            self.preprocessed_data_dict = host_view(host, self.ndc)
 
     def get_model_configs(self):
         return self.model_configs
@@ -253,7 +279,7 @@ class DataPreprocessor:
     # -------------------------------------------------------------------------------------------------- batches
     def get_next_batch(self, iter_num: int, image_num: Optional[int] = None, **kwargs):
         if self.assembler is None:
-            raise RuntimeError(f"get_next_batch: mode '{self.mode}' has no training scene (construct with mode='train')")
+            raise RuntimeError(f"get_next_batch: mode '{self.mode}' has no scene (construct with mode='train' or 'validation')")
         return self.assembler.get_next_batch(iter_num, image_num, **kwargs)
 
     # -------------------------------------------------------------------------------------------------- inference

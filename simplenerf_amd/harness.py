@@ -3,7 +3,8 @@ full-frame input batch -> ``model(batch)`` under no_grad -> display post-process
 multi-GPU variant (one process per GPU, contiguous block of rays per rank, one gather of the per-ray outputs).
 
 Reference call sites restated here: DataPreprocessor.create_test_data (src/data_preprocessors/DataPreprocessor01.py
-:807-895), NerfTester.predict_frame (src/Tester01.py:57-66), post_process_image/depth (:1106-1114).
+:807-895), NerfTester.predict_frame (src/Tester01.py:57-66), post_process_image/depth (:1106-1114), and the trainer's two
+frame loops, Trainer.run_validation (src/Trainer01.py:109-263) and save_sample_images (:319-350), at the end of this file.
 """
 from __future__ import annotations
 
@@ -132,6 +133,11 @@ def retrieve_inference_outputs(configs: dict, resolution, network_outputs: Dict[
     (h,w) float32 and, for NDC scenes, ``depth_ndc``, ``depth_var_ndc``; the suffix is ``_fine`` when the model has a
     fine MLP, else ``_coarse`` (:900-905); ``visibility2`` (nf-1, h, w) float32 when the outputs carry it
     (predict_visibility with secondary views, :919-924)."""
+    return {k: v.cpu().numpy() for k, v in display_outputs(configs, resolution, network_outputs).items()}
+
+
+def display_outputs(configs: dict, resolution, network_outputs: Dict[str, Tensor]) -> Dict[str, Tensor]:
+    """``retrieve_inference_outputs`` before the copy to the host: the same keys, as device tensors."""
     h, w = int(resolution[0]), int(resolution[1])
     if 'fine_mlp' in configs['model']:
         suffix = '_fine'
@@ -145,11 +151,10 @@ def retrieve_inference_outputs(configs: dict, resolution, network_outputs: Dict[
     for name in names:
         out[name] = ops.to_display(network_outputs[f'rgb{suffix}'].reshape(h * w, 3),
                                    network_outputs[f'{name}{suffix}'].reshape(h * w), colour=False)[1].reshape(h, w)
-    result = {k: v.cpu().numpy() for k, v in out.items()}
     if f'visibility2{suffix}' in network_outputs:
         vis2 = network_outputs[f'visibility2{suffix}'].reshape(h, w, -1).permute(2, 0, 1).contiguous()
-        result['visibility2'] = vis2.float().cpu().numpy()         # post_process_visibility: a float32 cast (:1116-1119)
-    return result
+        out['visibility2'] = vis2.float()                          # post_process_visibility: a float32 cast (:1116-1119)
+    return out
 
 
 @torch.no_grad()
@@ -640,13 +645,19 @@ def save_image(path, image) -> None:
 
 def save_depth(path, depth, as_png: bool = False) -> None:
     """``depth``: float (h,w); ``.npy`` keeps the values (plus a PNG preview when ``as_png``), ``.png`` stores
-    round(depth / depth.max() * 255) like the reference (src/Tester01.py:80-92)."""
+    round(depth / depth.max() * 255) like the reference (src/Tester01.py:80-92).  A float32 tensor on the device is converted
+    there (``ops.maps_to_u8``: the same bytes) and its preview copied as one byte per pixel."""
     import os
     import numpy
     path = os.fspath(path)
     os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
-    array = depth.cpu().numpy() if isinstance(depth, torch.Tensor) else numpy.asarray(depth)
-    preview = numpy.round(array / array.max() * 255).astype('uint8')
+    if isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32:
+        # the preview on the device (snerf_maps_to_u8): one byte per pixel crosses, and the floats only for a .npy
+        preview = ops.maps_to_u8(depth.reshape(1, -1), (ops.MAP_SCALE_MAX,))[0].reshape(depth.shape).cpu().numpy()
+        array = depth.cpu().numpy() if path.endswith('.npy') else None
+    else:
+        array = depth.cpu().numpy() if isinstance(depth, torch.Tensor) else numpy.asarray(depth)
+        preview = numpy.round(array / array.max() * 255).astype('uint8')
     if path.endswith('.png'):
         with open(path, 'wb') as f:
             f.write(_png_bytes(preview))
@@ -657,3 +668,195 @@ def save_depth(path, depth, as_png: bool = False) -> None:
                 f.write(_png_bytes(preview))
     else:
         raise RuntimeError(f'Unknown depth format: {path}')
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the trainer's two frame loops (src/Trainer01.py: run_validation :109-263, save_sample_images :319-350)
+# per-sample outputs the reference deletes from every chunk before merging (:197-221)
+VALIDATION_DROPPED_KEYS = tuple(
+    f'{stem}_{level}' for level in ('coarse', 'fine') for stem in (
+        'z_vals', 'z_vals_other', 'raw_sigma', 'raw_sigma_other', 'raw_rgb', 'raw_rgb_view_independent', 'raw_rgb_view_dependent',
+        'raw_rgb_other', 'raw_rgb_view_independent_other', 'raw_rgb_view_dependent_other', 'raw_visibility', 'raw_visibility2',
+        'alpha', 'visibility', 'weights', 'alpha_other', 'visibility_other', 'weights_other', 'rays_d2', 'rays_o2_ndc', 'rays_d2_ndc',
+        'rgb_other', 'acc_other', 'depth_other', 'depth_var_other', 'depth_ndc_other', 'depth_var_ndc_other'))
+
+
+def divide_batch(input_batch: dict, chunk_size: int) -> list:
+    """A frame's batch in consecutive chunks (:130-145): what has one row per ray is sliced, ``common_data`` is copied (the loss
+    computer unpacks it in place), everything else is shared."""
+    n = input_batch['rays_o'].shape[0]
+    chunks = []
+    for start in range(0, n, chunk_size):
+        chunk = {}
+        for key, value in input_batch.items():
+            if hasattr(value, 'shape') and len(value.shape) > 0 and value.shape[0] == n:
+                chunk[key] = value[start:start + chunk_size]
+            elif key == 'common_data':
+                chunk[key] = dict(value)
+            else:
+                chunk[key] = value
+        chunks.append(chunk)
+    return chunks
+
+
+def merge_chunks(chunks: list) -> dict:
+    """The reference's merge of per-chunk dictionaries (:147-172), model outputs and loss dictionaries alike: a tensor of more than
+    one element is concatenated along the rays, a one-element tensor (a loss value) becomes the PLAIN mean of the chunks' values --
+    a short last chunk weighs as much as a full one -- and dictionaries are merged by the same rule, two levels deep (a loss's
+    ``loss_value`` and its ``loss_maps``).  Anything else raises, as there."""
+    def merge(values, depth):
+        first = values[0]
+        if isinstance(first, torch.Tensor):
+            if depth == 2 or (depth == 0 and first.numel() > 1):
+                return torch.cat(values, dim=0)
+            if first.numel() == 1:
+                return torch.mean(torch.stack(values))
+        elif isinstance(first, dict) and depth < 2:
+            return {key: merge([v[key] for v in values], depth + 1) for key in first}
+        raise RuntimeError(f'merge_chunks: cannot merge {type(first).__name__} values at depth {depth}')
+
+    return {key: merge([chunk[key] for chunk in chunks], 0) for key in chunks[0]}
+
+
+def _validation_maps(outputs: dict, losses: Optional[dict], frame_num, frame_nums, iter_label: str):
+    """[(file name without suffix, float tensor, is colour)] of one frame, in the reference's order (:233-259)."""
+    maps = []
+    for level in ('coarse', 'fine'):
+        if f'rgb_{level}' not in outputs:
+            continue
+        stem = f'{frame_num:04}_{level}'
+        maps.append((f'predicted_frames/{stem}_{iter_label}', outputs[f'rgb_{level}'], True))
+        maps.append((f'predicted_depths/{stem}_{iter_label}', outputs[f'depth_{level}'], False))
+        if f'depth_ndc_{level}' in outputs:
+            maps.append((f'predicted_depths/{stem}_ndc_{iter_label}', outputs[f'depth_ndc_{level}'], False))
+        maps.append((f'predicted_depths_variance/{stem}_{iter_label}', outputs[f'depth_var_{level}'], False))
+        if f'depth_var_ndc_{level}' in outputs:
+            maps.append((f'predicted_depths_variance/{stem}_ndc_{iter_label}', outputs[f'depth_var_ndc_{level}'], False))
+        if f'visibility2_{level}' in outputs:
+            for j, other in enumerate(x for x in frame_nums if x != frame_num):
+                maps.append((f'predicted_visibilities/{frame_num:04}_{other:04}_{level}_{iter_label}',
+                             outputs[f'visibility2_{level}'][:, j], False))
+    for entry in (losses or {}).values():
+        if isinstance(entry, dict):
+            for fullname, loss_map in entry['loss_maps'].items():
+                maps.append((f'Losses/{fullname}_{frame_num:04}_{iter_label}', loss_map, False))
+    return maps
+
+
+def _convert_and_write(maps, resolution, frame_num, save_dirpath, keep, write_floats: bool = True) -> None:
+    """All maps of a frame through ONE ``ops.maps_to_u8`` call -- the colour as rows of mode 0 (save_image :384-387), every other map
+    with mode 1 (save_numpy_array :397-409) -- then the reference's files: a PNG for the colour, ``.npy`` + PNG for the rest
+    (``write_floats`` False: the PNG only, as save_sample_images writes)."""
+    import os
+    import numpy
+    h, w = int(resolution[0]), int(resolution[1])
+    n = h * w
+    rows, modes, spans = [], [], []
+    for stem, tensor, colour in maps:
+        flat = tensor.detach().reshape(-1).float()
+        if flat.numel() != (3 * n if colour else n):
+            raise RuntimeError(f'{stem}: {tuple(tensor.shape)} is not a {h}x{w} {"colour frame" if colour else "map"}')
+        spans.append((len(modes), flat.numel() // n))
+        rows.append(flat)
+        modes += [ops.MAP_SCALE_255 if colour else ops.MAP_SCALE_MAX] * (flat.numel() // n)
+    floats = torch.cat(rows).reshape(len(modes), n)
+    bytes_host = ops.maps_to_u8(floats, modes)[0].cpu().numpy()
+    floats_host = floats.cpu().numpy() if keep is not None or (save_dirpath is not None and write_floats) else None
+    for (stem, _, colour), (first, count) in zip(maps, spans):
+        shape = (h, w, 3) if colour else (h, w)
+        as_u8 = bytes_host[first:first + count].reshape(shape)
+        as_float = None if floats_host is None else floats_host[first:first + count].reshape(shape)
+        if keep is not None:
+            keep[(frame_num, stem)] = {'float': as_float, 'u8': as_u8}
+        if save_dirpath is not None:
+            path = os.path.join(os.fspath(save_dirpath), stem)
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            if not colour and write_floats:
+                numpy.save(path + '.npy', as_float)
+            with open(path + '.png', 'wb') as f:
+                f.write(_png_bytes(as_u8))
+
+
+def run_validation(model, loss_computer, data_preprocessor, iter_num: int, configs: dict, save_dirpath=None,
+                   keep: Optional[dict] = None) -> Dict[str, float]:
+    """Trainer.run_validation (src/Trainer01.py:109-263) over every view of ``data_preprocessor`` (a train- or validation-mode
+    DataPreprocessor), on one rank: the model goes to eval mode (:184) and back to train mode at the end (:262); every frame's
+    ``get_next_batch(iter_num, frame_num)`` is cut into chunks of ``configs['validation_chunk_size']``, each chunk rendered under
+    no_grad as ``model(chunk, retraw=True, sec_views_vis=(data_preprocessor.mode == 'train'))`` and scored by
+    ``compute_losses(chunk, out, return_loss_maps=configs['validation_save_loss_maps'])``; the per-sample outputs are dropped
+    (:197-221) and the chunks merged by ``merge_chunks``.  Returns {loss name: mean over the frames of the frame's merged value}
+    as Python floats (:110-122, :260-261); the loss values of a frame cross to the host in one copy.
+
+    ``save_dirpath``: the reference's files under the reference's names (:233-259) -- ``predicted_frames/<frame>_<level>_Iter<n>.png``,
+    and ``.npy`` + ``.png`` under ``predicted_depths/``, ``predicted_depths_variance/`` (with ``_ndc`` forms), ``predicted_visibilities/``
+    and ``Losses/`` -- the 8-bit images from one ``ops.maps_to_u8`` call per frame, written by this module's PNG writer.
+    ``keep``: a dict that receives ``{(frame_num, file name without suffix, relative to save_dirpath): {'float': array, 'u8': array}}``
+    for the same arrays, with or without a directory.
+
+    A loss list that reads outputs an eval-mode model does not produce fails here as it does in the reference: the augmentation
+    models run in training mode only (src/models/SimpleNeRF01.py:170, :186), so PointsAugmentationDepthLoss02 and its siblings index
+    a missing key -- every shipped experiment sets ``validation_interval`` beyond ``num_iterations`` (NerfLlffTrainerTester01.py
+    :438-441).  A loss whose result carries no ``loss_maps`` (the SparseDepthMSE family) fails with ``validation_save_loss_maps``
+    as at :256; CoarseFineConsistencyLoss02 needs ``common_data``, which held-out views do not carry."""
+    resolution = data_preprocessor.preprocessed_data_dict['nerf_data']['resolution']
+    chunk_size = int(configs['validation_chunk_size'])
+    with_maps = bool(configs['validation_save_loss_maps'])
+    train_data = data_preprocessor.mode == 'train'
+    frame_nums = [int(f) for f in data_preprocessor.preprocessed_data_dict['frame_nums']]
+    iter_label = f'Iter{iter_num + 1:05}'
+    totals: Optional[Dict[str, float]] = None
+    model.eval()
+    for frame_num in frame_nums:
+        outputs, losses = [], []
+        for chunk in divide_batch(data_preprocessor.get_next_batch(iter_num, frame_num), chunk_size):
+            with torch.no_grad():
+                out = model(chunk, retraw=True, sec_views_vis=train_data)
+            losses.append(loss_computer.compute_losses(chunk, out, return_loss_maps=with_maps))
+            outputs.append({key: value for key, value in out.items() if key not in VALIDATION_DROPPED_KEYS})
+        frame_outputs, frame_losses = merge_chunks(outputs), merge_chunks(losses)
+        names = list(frame_losses) if totals is None else list(totals)
+        values = torch.stack([(frame_losses[name]['loss_value'] if isinstance(frame_losses[name], dict) else frame_losses[name])
+                              .detach().reshape(()).float() for name in names]).cpu().tolist()
+        if totals is None:
+            totals = dict.fromkeys(names, 0.0)
+        for name, value in zip(names, values):
+            totals[name] += value
+        if save_dirpath is not None or keep is not None:
+            maps = _validation_maps(frame_outputs, frame_losses if with_maps else None, frame_num, frame_nums, iter_label)
+            _convert_and_write(maps, resolution, frame_num, save_dirpath, keep)
+    model.train()
+    return {name: value / len(frame_nums) for name, value in (totals or {}).items()}
+
+
+def save_sample_images(model, configs: dict, preprocessors, iter_num: int, save_dirpath, keep: Optional[dict] = None) -> None:
+    """Trainer.save_sample_images (:319-350): every view of every preprocessor in ``preprocessors`` (the reference's pair: train,
+    validation) rendered from its stored processed pose -- ``create_test_data(pose, preprocess_pose=False)`` of the FIRST
+    preprocessor, the model under no_grad in eval mode, the outputs of ``retrieve_inference_outputs`` (8-bit colour, depths clipped
+    at 0; ``display_outputs``: they stay on the device) -- and written as PNGs: ``predicted_frames/<frame>_Iter<n>.png``,
+    ``predicted_depths[_variance]/<frame>[_ndc]_Iter<n>.png``.  The depth previews come from one ``ops.maps_to_u8`` call per frame, so a
+    frame crosses to the host as bytes.  ``keep`` as in ``run_validation`` (the colour has no 'float' entry)."""
+    import os
+    import numpy
+    first = preprocessors[0]
+    resolution = first.get_model_configs()['resolution']
+    iter_label = f'Iter{iter_num:05}'
+    model.eval()
+    for preprocessor in preprocessors:
+        view = preprocessor.preprocessed_data_dict
+        for frame_num, pose in zip(view['frame_nums'].tolist(), view['nerf_data']['poses']):
+            if pose.shape[0] == 3:
+                pose = numpy.concatenate([pose, numpy.array([0, 0, 0, 1], dtype=pose.dtype)[None]], axis=0)
+            with torch.no_grad():
+                outputs = model(first.create_test_data(pose, preprocess_pose=False))
+            predictions = display_outputs(first.configs, resolution, outputs)
+            names = [(f'predicted_depths/{frame_num:04}_{iter_label}', 'depth'), (f'predicted_depths/{frame_num:04}_ndc_{iter_label}', 'depth_ndc'),
+                     (f'predicted_depths_variance/{frame_num:04}_{iter_label}', 'depth_var'),
+                     (f'predicted_depths_variance/{frame_num:04}_ndc_{iter_label}', 'depth_var_ndc')]
+            maps = [(stem, predictions[name], False) for stem, name in names if name in predictions]
+            _convert_and_write(maps, resolution, frame_num, save_dirpath, keep, write_floats=False)
+            stem = f'predicted_frames/{frame_num:04}_{iter_label}'
+            image = predictions['image'].cpu().numpy()
+            if keep is not None:
+                keep[(frame_num, stem)] = {'u8': image}
+            save_image(os.path.join(os.fspath(save_dirpath), stem + '.png'), image)
+    model.train()

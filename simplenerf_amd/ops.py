@@ -579,6 +579,37 @@ def to_display(rgb: Optional[Tensor], depth: Optional[Tensor] = None, colour: bo
     return image, depth_out
 
 
+MAP_SCALE_255, MAP_SCALE_MAX = 0, 1      # the modes of snerf_maps_to_u8: rint(x * 255); rint(x / max(x) * 255)
+_map_modes: Dict[tuple, Tensor] = {}
+
+
+def maps_to_u8(maps: Tensor, modes):
+    """-> (uint8 (K, n), int32 status (K)) on the device, for ``maps`` (K, n) float32 and one mode per map: 0 = ``rint(x * 255)``
+    (the reference's save_image; a colour frame is three rows of mode 0), 1 = ``rint(x / max(x) * 255)`` (its save_numpy_array
+    preview), in numpy's float32 arithmetic, saturating to 0..255.  Status 1: a mode-1 map whose maximum is not a positive finite
+    number (its row is zeros).  All K maps go through two launches; a contiguous view is taken as it is, wherever it starts."""
+    maps = _dev(maps, 'maps')
+    if maps.dim() != 2:
+        raise RuntimeError(f'maps: expected shape (K, n), got {tuple(maps.shape)}')
+    modes = tuple(int(m) for m in modes)
+    count, n = int(maps.shape[0]), int(maps.shape[1])
+    if len(modes) != count or any(m not in (MAP_SCALE_255, MAP_SCALE_MAX) for m in modes):
+        raise RuntimeError(f'modes: expected {count} values of 0 or 1, got {modes}')
+    dev = maps.device
+    out = torch.empty((count, n), dtype=torch.uint8, device=dev)
+    status = torch.zeros((count,), dtype=torch.int32, device=dev)
+    if count == 0 or n == 0:
+        return out, status
+    on_device = _map_modes.get((modes, dev))
+    if on_device is None:
+        if len(_map_modes) > 64:
+            _map_modes.clear()
+        on_device = _map_modes[(modes, dev)] = torch.tensor(modes, dtype=torch.int32, device=dev)
+    workspace = _workspace('maps_u8', dev, int(_lib.load().snerf_maps_to_u8_workspace_bytes(count)))
+    _enqueue('snerf_maps_to_u8', dev, _ptr(maps), _ptr(on_device), count, n, _ptr(out), _ptr(status), _ptr(workspace))
+    return out, status
+
+
 # ---------------------------------------------------------------------------------------------- Q1 frame metrics
 def _typed(t, name: str, dtypes, shape=None) -> Tensor:
     """Validate a device operand of one of ``dtypes`` (the metric inputs are uint8 / bool / float32); contiguous on return."""
