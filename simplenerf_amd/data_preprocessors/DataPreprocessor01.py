@@ -283,13 +283,9 @@ class DataPreprocessor:
         return self.assembler.get_next_batch(iter_num, image_num, **kwargs)
 
     # -------------------------------------------------------------------------------------------------- inference
-    def create_test_data(self, pose: numpy.ndarray, view_pose=None, secondary_poses=None, preprocess_pose: bool = True,
-                         intrinsic: Optional[numpy.ndarray] = None, view_intrinsic=None, secondary_intrinsics=None):
-        if view_pose is not None or view_intrinsic is not None:
-            raise NotImplementedError("create_test_data(view_pose=...): rendering a pose under another camera's view directions is "
-                                      "not part of this build")
-        if secondary_poses is not None or secondary_intrinsics is not None:
-            raise NotImplementedError('create_test_data(secondary_poses=...): secondary-view origins (rays_o2) are not built here')
+    def camera(self, pose: numpy.ndarray, intrinsic: Optional[numpy.ndarray] = None, preprocess_pose: bool = True) -> dict:
+        """The camera dict of ``harness.frame_batch`` for a raw pose (``preprocess_pose``: recentred and scaled like the training
+        poses) or an already processed one, with the scene's intrinsic unless one is given."""
         if self.model_configs is None:
             raise RuntimeError('create_test_data: no model configs (train mode derives them; other modes are given them)')
         cfg = self.model_configs
@@ -303,7 +299,18 @@ class DataPreprocessor:
                   'near': cfg['near'], 'far': cfg['far']}
         if self.ndc:
             camera.update(near_ndc=cfg['near_ndc'], far_ndc=cfg['far_ndc'])
-        return harness.frame_batch(camera, self.ndc, self.device)
+        return camera
+
+    def create_test_data(self, pose: numpy.ndarray, view_pose=None, secondary_poses=None, preprocess_pose: bool = True,
+                         intrinsic: Optional[numpy.ndarray] = None, view_intrinsic=None, secondary_intrinsics=None):
+        if view_pose is not None or view_intrinsic is not None:
+            raise NotImplementedError("create_test_data(view_pose=...): rendering a pose under another camera's view directions is "
+                                      "not part of this call -- use harness.frame_batch(self.camera(pose), ndc, device, "
+                                      "view_camera=self.camera(view_pose, view_intrinsic)) or harness.predict_view_sweep")
+        if secondary_poses is not None or secondary_intrinsics is not None:
+            raise NotImplementedError('create_test_data(secondary_poses=...): secondary-view origins (rays_o2) are not built by this '
+                                      'call -- use harness.frame_batch(..., secondary_cameras=[self.camera(p) for p in secondary_poses])')
+        return harness.frame_batch(self.camera(pose, intrinsic, preprocess_pose), self.ndc, self.device)
 
     def retrieve_inference_outputs(self, network_outputs: dict):
         return harness.retrieve_inference_outputs(self.configs, self.model_configs['resolution'], network_outputs)

@@ -8,11 +8,12 @@ frame loops, Trainer.run_validation (src/Trainer01.py:109-263) and save_sample_i
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Dict, Iterable, Optional, Tuple
 
 import torch
 
-from . import ops
+from . import _lib, ops
 from .models.SimpleNeRFHip01 import global_rows
 
 Tensor = torch.Tensor
@@ -48,30 +49,49 @@ def _constant_column(value: float, rows: int, device: torch.device) -> Tensor:
     return col
 
 
-def frame_batch(camera: dict, ndc: bool, device, first_ray: int = 0, num_rays: Optional[int] = None) -> Dict[str, Tensor]:
-    """Input dictionary for rays [first_ray, first_ray+num_rays) of a frame, generated on the device (K1)."""
+def frame_batch(camera: dict, ndc: bool, device, first_ray: int = 0, num_rays: Optional[int] = None,
+                view_camera: Optional[dict] = None, secondary_cameras: Optional[Iterable[dict]] = None) -> Dict[str, Tensor]:
+    """Input dictionary for rays [first_ray, first_ray+num_rays) of a frame, generated on the device (K1).
+
+    ``view_camera`` (a dict like ``camera``): ``view_dirs`` are those of that camera's rays through the same pixels -- the
+    reference's ``create_test_data(pose, view_pose, ..., view_intrinsic)`` (src/data_preprocessors/DataPreprocessor01.py:832-843).
+    ``secondary_cameras``: adds ``rays_o2`` (n, K, 3), every secondary camera's centre repeated per ray (:871-885)."""
     h, w = camera['resolution']
     if num_rays is None:
         num_rays = h * w - first_ray
     batch = ops.generate_rays((h, w), camera['intrinsic'], camera['pose'], camera['near'], ndc, device, first_ray, num_rays)
+    if view_camera is not None:
+        batch['view_dirs'] = view_directions(camera, view_camera, device, first_ray, num_rays)
     col = lambda v: _constant_column(float(v), num_rays, torch.device(device))
     batch['near'], batch['far'] = col(camera['near']), col(camera['far'])
     if ndc:
         batch['near_ndc'], batch['far_ndc'] = col(camera.get('near_ndc', 0.0)), col(camera.get('far_ndc', 1.0))
+    if secondary_cameras is not None:
+        import numpy
+        centres = numpy.array([numpy.asarray(c['pose'], dtype=numpy.float32)[:3, 3] for c in secondary_cameras],
+                              dtype=numpy.float32).reshape(-1, 3)                                                  # (K,3)
+        batch['rays_o2'] = torch.from_numpy(centres).to(device)[None].expand(num_rays, -1, -1).contiguous()
     return batch
+
+
+def view_directions(camera: dict, view_camera: dict, device, first_ray: int = 0, num_rays: Optional[int] = None) -> Tensor:
+    """(n,3) unit directions of ``view_camera``'s rays through pixels [first_ray, first_ray+num_rays) of ``camera``'s frame: a ray
+    generation of which only the view directions are kept (they do not depend on ``ndc`` or ``near``)."""
+    return ops.generate_rays(camera['resolution'], view_camera['intrinsic'], view_camera['pose'], camera['near'], False, device,
+                             first_ray, num_rays)['view_dirs']
 
 
 @torch.no_grad()
 def render_rays_blockwise(model, camera: dict, ndc: bool, device, first_ray: int, num_rays: int,
-                          keys: Iterable[str] = DEFAULT_KEYS, ray_block: int = 65536) -> Dict[str, Tensor]:
-    """Render a ray range in blocks (bounding the per-sample buffers), keeping only ``keys``."""
+                          keys: Iterable[str] = DEFAULT_KEYS, ray_block: int = 65536, view_camera: Optional[dict] = None) -> Dict[str, Tensor]:
+    """Render a ray range in blocks (bounding the per-sample buffers), keeping only ``keys``.  ``view_camera``: as ``frame_batch``."""
     keys = tuple(keys)
     pieces = {k: [] for k in keys}
     # a rank that owns no rays (ceil-division shards of a tiny frame) still runs one zero-ray call, so that its
     # outputs have the right trailing shapes for the gather
     for start in (range(first_ray, first_ray + num_rays, ray_block) if num_rays > 0 else (first_ray,)):
         count = min(ray_block, first_ray + num_rays - start)
-        out = model(frame_batch(camera, ndc, device, start, count))
+        out = model(frame_batch(camera, ndc, device, start, count, view_camera=view_camera))
         for k in keys:
             pieces[k].append(out[k])
     return {k: torch.cat(v, 0) for k, v in pieces.items()}
@@ -104,14 +124,15 @@ def gather_rays(local: Dict[str, Tensor], num_rays: int, rank: int, world_size: 
 
 @torch.no_grad()
 def render_frame(model, camera: dict, ndc: bool, device, keys: Iterable[str] = DEFAULT_KEYS, rank: int = 0,
-                 world_size: int = 1, ray_block: int = 65536, collective: Optional[bool] = None) -> Optional[Dict[str, Tensor]]:
+                 world_size: int = 1, ray_block: int = 65536, collective: Optional[bool] = None,
+                 view_camera: Optional[dict] = None) -> Optional[Dict[str, Tensor]]:
     """Full frame, (h*w, .) per key.  With world_size > 1 every rank renders its block and rank 0 receives the
     frame through one gather (returns None on the other ranks).  ``collective=True`` issues that gather with a single rank
-    too (a one-rank process group: the RCCL call path of the multi-GPU run on a one-GPU box)."""
+    too (a one-rank process group: the RCCL call path of the multi-GPU run on a one-GPU box).  ``view_camera``: as ``frame_batch``."""
     h, w = camera['resolution']
     n = h * w
     first, count = shard_range(n, rank, world_size)
-    local = render_rays_blockwise(model, camera, ndc, device, first, count, keys, ray_block)
+    local = render_rays_blockwise(model, camera, ndc, device, first, count, keys, ray_block, view_camera)
     if not (world_size > 1 if collective is None else collective):
         return local
     return gather_rays(local, n, rank, world_size)
@@ -159,17 +180,127 @@ def display_outputs(configs: dict, resolution, network_outputs: Dict[str, Tensor
 
 @torch.no_grad()
 def predict_frame(model, configs: dict, camera: dict, device, rank: int = 0, world_size: int = 1,
-                  ray_block: int = 65536, collective: Optional[bool] = None) -> Optional[dict]:
+                  ray_block: int = 65536, collective: Optional[bool] = None, view_camera: Optional[dict] = None) -> Optional[dict]:
     """NerfTester.predict_frame (src/Tester01.py:57-66): full-frame batch -> model under no_grad -> the five display
     outputs.  Rays are generated on the device per block; with world_size > 1 each rank renders its block of the frame
-    and rank 0 receives it through one gather (None on the other ranks)."""
+    and rank 0 receives it through one gather (None on the other ranks).  ``view_camera``: as ``frame_batch``."""
     ndc = bool(configs['data_loader']['ndc'])
     suffix = '_fine' if 'fine_mlp' in configs['model'] else '_coarse'
     keys = [f'rgb{suffix}', f'depth{suffix}', f'depth_var{suffix}'] + ([f'depth_ndc{suffix}', f'depth_var_ndc{suffix}'] if ndc else [])
-    frame = render_frame(model, camera, ndc, device, keys, rank, world_size, ray_block, collective)
+    frame = render_frame(model, camera, ndc, device, keys, rank, world_size, ray_block, collective, view_camera)
     if frame is None:
         return None
     return retrieve_inference_outputs(configs, camera['resolution'], frame)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# static-camera view sweep: the reference's start_testing_static_videos (one pose, the view directions of every camera of a path)
+SWEEP_ACTIVATION_BYTES = 8 << 30      # what the saved activations + sweep scratch of one ray block may take on the fast route
+
+
+def _sweep_levels(model):
+    """[(C-ABI level, module)] of the MLPs an eval-mode render runs; the last one is the displayed level."""
+    return [(0, model.coarse_model)] + ([(3, model.fine_model)] if model.fine_mlp_needed else [])
+
+
+def view_sweep_is_fast(model) -> bool:
+    """Whether ``predict_view_sweep`` takes the one-trunk-pass route for ``model``: an fp32 model whose displayed MLP is a shape
+    ``snerf_view_sweep`` is built for (the library decides: its workspace query is 0 for every other descriptor) and none of
+    whose MLPs predicts visibility."""
+    if not hasattr(model, 'coarse_model') or model.precision != ops.PRECISION_FP32:
+        return False
+    levels = _sweep_levels(model)
+    if any(module.predict_visibility for _, module in levels):
+        return False
+    desc = ops.mlp_desc(levels[-1][1].mlp_configs)
+    return int(_lib.load().snerf_view_sweep_workspace_floats(ctypes.byref(desc), 1, 1, 1)) > 0
+
+
+def _sweep_ray_block(model, num_views: int) -> int:
+    """Rays per block so that the saved activations of every level plus the sweep's scratch stay under SWEEP_ACTIVATION_BYTES
+    (8 x 256 at 64 + 128 samples: ~2.6 MB of activations per ray, so ~3000 rays)."""
+    lib = _lib.load()
+    mcfg = model.configs['model']
+    s_c = int(mcfg['coarse_mlp']['num_samples'])
+    floats = 0           # of 1024 rays
+    for level, module in _sweep_levels(model):
+        samples = s_c + (int(mcfg['fine_mlp']['num_samples']) if level == 3 else 0)
+        desc = ops.mlp_desc(module.mlp_configs)
+        floats += int(lib.snerf_mlp_saved_floats(ctypes.byref(desc), 1024, samples))
+    floats += int(lib.snerf_view_sweep_workspace_floats(ctypes.byref(desc), 1024, samples, num_views))     # (the displayed level's)
+    return max(32, int(SWEEP_ACTIVATION_BYTES * 1024 // (4 * floats)))
+
+
+@torch.no_grad()
+def predict_view_sweep(model, configs: dict, camera: dict, view_cameras, device, ray_block: Optional[int] = None) -> dict:
+    """``camera``'s frame under the view directions of each of ``view_cameras`` (dicts like ``camera``): the eval-mode render of
+    the reference's static-camera video (src/Tester01.py start_testing with ``extrinsic_viewcam``), on one rank.
+
+    Returns {'images': (V,h,w,3) uint8 array, 'rgb': (V,h*w,3) float32 on the device, 'depth', 'depth_var' (and, for NDC scenes,
+    'depth_ndc', 'depth_var_ndc'): (h,w) float32 arrays} -- the maps do not depend on the view camera and are there once, converted
+    as ``retrieve_inference_outputs`` converts them.
+
+    Fast route (``view_sweep_is_fast``): per block of ``ray_block`` rays ONE render that keeps the activations
+    (``ops.render_keep_activations``), ONE ``ops.view_sweep`` over all V cameras and one display conversion per view; everything up
+    to the views layer's pre-activation is computed once, not V times.  ``ray_block`` defaults to what keeps a block's saved
+    activations and scratch under SWEEP_ACTIVATION_BYTES.  Every other model (other precisions, layered shapes, predict_visibility)
+    takes the plain loop, one ordinary render per view camera (``frame_batch(view_camera=...)``, blocks of ``ray_block`` or 65536
+    rays), with the answer in the same form."""
+    view_cameras = list(view_cameras)
+    h, w = int(camera['resolution'][0]), int(camera['resolution'][1])
+    n, count = h * w, len(view_cameras)
+    ndc = bool(configs['data_loader']['ndc'])
+    map_names = ['depth', 'depth_var'] + (['depth_ndc', 'depth_var_ndc'] if ndc else [])
+    rgb = torch.empty((count, n, 3), dtype=torch.float32, device=device)
+    images = torch.empty((count, n, 3), dtype=torch.uint8, device=device)
+    maps: Dict[str, Tensor] = {}
+    if not view_sweep_is_fast(model):
+        suffix = '_fine' if 'fine_mlp' in configs['model'] else '_coarse'
+        keys = [f'rgb{suffix}'] + [f'{name}{suffix}' for name in map_names]
+        for v, view_camera in enumerate(view_cameras):
+            frame = render_frame(model, camera, ndc, device, keys, ray_block=ray_block or 65536, view_camera=view_camera)
+            shown = display_outputs(configs, (h, w), frame)
+            rgb[v], images[v] = frame[f'rgb{suffix}'], shown['image'].reshape(n, 3)
+            if v == 0:
+                maps = {name: shown[name] for name in map_names}
+    elif count > 0:
+        mcfg = configs['model']
+        levels = _sweep_levels(model)
+        packed = [None] * 6
+        for level, module in levels:
+            packed[level] = model._packed_mlp('coarse_model' if level == 0 else 'fine_model', True)
+        shown_level, shown_module = levels[-1]
+        params = shown_module.abi_params()
+        white = bool(mcfg['white_bkgd'])
+        block = int(ray_block or _sweep_ray_block(model, count))
+        maps = {name: torch.empty((n,), dtype=torch.float32, device=device) for name in map_names}
+        for first in range(0, n, block):
+            rays = min(block, n - first)
+            kept = ops.render_keep_activations(packed, frame_batch(camera, ndc, device, first, rays), ndc, white, bool(mcfg['lindisp']),
+                                               int(mcfg['coarse_mlp']['num_samples']),
+                                               int(mcfg['fine_mlp']['num_samples']) if shown_level == 3 else 0)
+            dirs = torch.stack([view_directions(camera, view_camera, device, first, rays) for view_camera in view_cameras])
+            swept = ops.view_sweep(packed[shown_level], params, kept['saved_acts'], kept['weights'], kept['acc'], dirs, white)
+            rgb[:, first:first + rays] = swept
+            for v in range(count):
+                images[v, first:first + rays] = ops.to_display(swept[v], None)[0]
+            for name in map_names:
+                maps[name][first:first + rays] = ops.to_display(None, kept['outputs'][name], colour=False)[1]
+    out = {'images': images.reshape(count, h, w, 3).cpu().numpy(), 'rgb': rgb}
+    out.update({name: value.reshape(h, w).cpu().numpy() for name, value in maps.items()})
+    return out
+
+
+def save_static_camera_frames(model, configs: dict, preprocessor, extrinsics, out_dirpath, device) -> dict:
+    """The frames of the reference's StaticCameraVideo (start_testing_static_videos + Tester.start_testing): ``extrinsics`` (N,4,4)
+    raw poses; the frame of ``extrinsics[0]`` under the view cameras ``extrinsics[1:]`` (``predict_view_sweep``), written as
+    ``predicted_frames/{i:04}.png`` for i = 0 .. N-2 under ``out_dirpath``.  The mp4 is not written.  Returns the sweep's result."""
+    import os
+    cameras = [preprocessor.camera(pose) for pose in extrinsics]
+    result = predict_view_sweep(model, configs, cameras[0], cameras[1:], device)
+    for i, image in enumerate(result['images']):
+        save_image(os.path.join(os.fspath(out_dirpath), 'predicted_frames', f'{i:04}.png'), image)
+    return result
 
 
 @torch.no_grad()

@@ -435,7 +435,8 @@ class RenderCall:
             out[l][name] = view(slot)
         saved = [torch.empty((lib.snerf_mlp_saved_floats(ctypes.byref(self.mlps[l].desc), n, samples[l]),), dtype=torch.float32,
                              device=dev) for l in self.levels] if self.keep else []
-        for l, t in zip(self.levels, saved):
+        self.saved = dict(zip(self.levels, saved))      # level -> its saved activations (keep_activations only)
+        for l, t in self.saved.items():
             o.level[l].saved_acts = t.data_ptr()
         work = None
         if lay.needs_workspace:
@@ -488,6 +489,52 @@ class RenderCall:
             st = lib.snerf_render_backward(ctypes.byref(self.cfg), self.c_mlps, ctypes.byref(self.c_rays), n,
                                            ctypes.byref(self.c_out), c_grads, _ptr(work), _stream())
         _lib.check(st, 'snerf_render_backward')
+
+
+# ---------------------------------------------------------------------------------------------- view sweep
+@torch.no_grad()
+def render_keep_activations(mlps: List[Optional['PackedMlp']], rays: Dict[str, Tensor], ndc: bool, white_bkgd: bool, lindisp: bool,
+                            num_coarse: int, num_fine: int, z_vals_fine: Optional[Tensor] = None) -> Dict[str, object]:
+    """One ``snerf_render_forward`` that keeps the activations without recording a backward: fp32, no jitter, no density noise.
+    ``mlps`` as ``RenderCall`` takes them, packed for the training layout (the storing forward reads it).  Returns, for the level a
+    frame is displayed from (the fine MLP's, the coarse one's without a fine MLP): 'level', 'num_samples', 'saved_acts',
+    'weights' (n,S), 'acc' (n,) and 'outputs', that level's per-ray outputs by name (rgb, acc, depth, depth_var, ...)."""
+    call = RenderCall(mlps, ndc, white_bkgd, lindisp, num_coarse, num_fine, PRECISION_FP32, keep_activations=True,
+                      per_sample=('alpha', 'weights'))
+    draws = {} if z_vals_fine is None else {'z_vals_fine': z_vals_fine}
+    _, _, levels = call.forward(rays, draws)
+    level = 3 if call.mlps[3] is not None else 0
+    out = levels[level]
+    return {'level': level, 'num_samples': call.layout.samples[level], 'saved_acts': call.saved[level], 'weights': out['weights'],
+            'acc': out['acc'], 'outputs': out}
+
+
+def view_sweep(mlp: 'PackedMlp', params: List[Tensor], saved_acts: Tensor, weights: Tensor, acc: Optional[Tensor], view_dirs: Tensor,
+               white_bkgd: bool = False) -> Tensor:
+    """snerf_view_sweep (csrc/simplenerf_sweep.h): the colour (V,n,3) of n composited rays under V sets of view directions
+    (V,n,3), from the fp32 activations ``saved_acts`` a storing forward of ``mlp`` kept for these rays, their ``weights`` (n,S) and
+    -- with ``white_bkgd`` -- ``acc`` (n,).  ``params``: the MLP's parameter tensors in C-ABI order, as ``PackedMlp.pack`` takes them."""
+    lib = _lib.load()
+    n, s = weights.shape
+    v = view_dirs.shape[0]
+    weights = _dev(weights, 'weights', (n, s))
+    acc = _dev(acc, 'acc', (n,)) if white_bkgd else None
+    view_dirs = _dev(view_dirs, 'view_dirs', (v, n, 3))
+    saved_acts = _dev(saved_acts, 'saved_acts')
+    dev = weights.device
+    need = int(lib.snerf_mlp_saved_floats(ctypes.byref(mlp.desc), n, s))
+    if saved_acts.numel() < need:
+        raise RuntimeError(f'saved_acts: {saved_acts.numel()} floats, {n} rays x {s} samples of this MLP keep {need}')
+    if len(params) != mlp.num_params:
+        raise RuntimeError(f'expected {mlp.num_params} parameter tensors, got {len(params)}')
+    held = [_dev(p, f'param[{i}]') for i, p in enumerate(params)]
+    arr = (ctypes.c_void_p * len(held))(*[p.data_ptr() for p in held])
+    out = torch.empty((v, n, 3), dtype=torch.float32, device=dev)
+    floats = int(lib.snerf_view_sweep_workspace_floats(ctypes.byref(mlp.desc), n, s, v))
+    work = _workspace('view_sweep', dev, 4 * floats) if floats else None
+    _enqueue('snerf_view_sweep', dev, ctypes.byref(mlp.desc), arr, len(held), _ptr(saved_acts), _ptr(weights), _ptr(acc),
+             _ptr(view_dirs), n, s, v, int(bool(white_bkgd)), _ptr(out), _ptr(work))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------- K4
