@@ -1,15 +1,17 @@
 // snerf_view_sweep (simplenerf_sweep.h): one pose under the view directions of V cameras, from the `feature` tiles a storing fp32
 // forward has left in the saved activations.  Four launches, all in stream order:
 //   1. sweep_transpose_kernel   W_v[:, :W] -> k-major wvt[i][j] in the workspace (the A operand rows of the matrix-core loop)
-//   2. sweep_view_bias_kernel   u[v,n,:] = b_v + W_v[:, W:] . PE(d[v,n]), one wave per (view, ray)
+//   2. sweep_view_bias_kernel   (view_sweep_tail.h) u[v,n,:] = b_v + W_v[:, W:] . PE(d[v,n]), one wave per (view, ray)
 //   3. sweep_block_kernel       one wave per 32-sample block: g = W_v[:, :W] . feature on v_mfma_f32_32x32x2_f32 -- the saved
 //                               [feature][32 samples] tile IS the B operand -- kept in VT accumulator tiles while the loop over the
 //                               views adds u, applies the ReLU and the 3 x Wv head on the VALU and writes weights * rgb per sample
-//   4. sweep_fold_kernel        out[v,n,c] = the samples' products summed s = 0 .. S-1 by one thread: a fixed order that does not
-//                               depend on how the ray's samples fall into the 32-sample blocks
+//                               (sweep_tail, view_sweep_tail.h: shared with the 16-bit sweep)
+//   4. sweep_fold_kernel        (view_sweep_tail.h) out[v,n,c] = the samples' products summed s = 0 .. S-1 by one thread: a fixed
+//                               order that does not depend on how the ray's samples fall into the 32-sample blocks
 // DESIGN.md section 9 has the reasons for each choice and the measured numbers.
 #include "mlp_device.h"
 #include "simplenerf_sweep.h"
+#include "view_sweep_tail.h"
 #include "wave.h"
 
 namespace {
@@ -32,37 +34,6 @@ __global__ void __launch_bounds__(256) sweep_transpose_kernel(const float* __res
     if (t >= width * views_width) return;
     const int i = t / views_width, j = t - i * views_width;
     wvt[t] = wv[(long long)j * ld + i];
-}
-
-// One wave per (view, ray): the encoding in LDS (reference order: x, then sin / cos of every frequency), then two (Wv = 128) or one
-// output feature per lane, e ascending.
-__global__ void __launch_bounds__(64) sweep_view_bias_kernel(const float* __restrict__ wv, const float* __restrict__ bv, int ld,
-                                                             int width, int views_width, int degree,
-                                                             const float* __restrict__ view_dirs, long long pairs,
-                                                             float* __restrict__ u) {
-    __shared__ float pe[3 + 6 * snerf::kMaxViewsDegree];
-    const int lane = threadIdx.x;
-    const int terms = 3 + 6 * degree;
-    for (long long p = blockIdx.x; p < pairs; p += gridDim.x) {
-        const float* d = view_dirs + 3 * p;
-        if (lane < 3 * degree) {
-            const int k = lane / 3, dim = lane - 3 * k;
-            float s, c;
-            sincos_turns((double)d[dim] * 0.15915494309189533576888 * (double)(1 << k), s, c);
-            pe[3 + 6 * k + dim] = s;
-            pe[6 + 6 * k + dim] = c;
-        } else if (lane >= 32 && lane < 35) {
-            pe[lane - 32] = d[lane - 32];
-        }
-        snerf::wave_lds_sync();
-        for (int j = lane; j < views_width; j += 64) {
-            const float* row = wv + (long long)j * ld + width;
-            float s = bv[j];
-            for (int e = 0; e < terms; ++e) s = fmaf(row[e], pe[e], s);
-            u[p * views_width + j] = s;
-        }
-        snerf::wave_lds_sync();
-    }
 }
 
 // Four waves per workgroup, one 32-sample block each (neighbouring blocks: the four waves read the same rows of wvt at about the
@@ -99,55 +70,7 @@ __global__ void __launch_bounds__(256, 2) sweep_block_kernel(SweepArgs a) {
     const bool live = sample < a.total;
     const long long ray = live ? sample / a.samples : a.num_rays - 1;
     const float weight = live ? a.weights[sample] : 0.0f;
-    const float b0 = head[3 * WV], b1 = head[3 * WV + 1], b2 = head[3 * WV + 2];
-#pragma unroll 1
-    for (int v = 0; v < a.views; ++v) {
-        asm volatile("" ::: "memory");      // the head weights are read from LDS per view, not hoisted into 3 x Wv / 2 registers
-        const float* uv = a.u + ((long long)v * a.num_rays + ray) * WV + 4 * h;
-        float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f;
-#pragma unroll
-        for (int t = 0; t < VT; ++t) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int f = 32 * t + 8 * g;       // + 4 h: in the pointers
-                const f32x4 uu = *reinterpret_cast<const f32x4*>(uv + f);
-                const f32x4 w0 = *reinterpret_cast<const f32x4*>(head + 4 * h + f);
-                const f32x4 w1 = *reinterpret_cast<const f32x4*>(head + WV + 4 * h + f);
-                const f32x4 w2 = *reinterpret_cast<const f32x4*>(head + 2 * WV + 4 * h + f);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float x = fmaxf(acc[t][4 * g + q] + uu[q], 0.0f);
-                    p0 = fmaf(w0[q], x, p0);
-                    p1 = fmaf(w1[q], x, p1);
-                    p2 = fmaf(w2[q], x, p2);
-                }
-            }
-        }
-        p0 += __shfl_xor(p0, 32, 64);
-        p1 += __shfl_xor(p1, 32, 64);
-        p2 += __shfl_xor(p2, 32, 64);
-        if (live && h == 0) {
-            float* out = a.products + (long long)v * 3 * a.total + sample;
-            out[0] = weight * sigmoidf(p0 + b0);
-            out[a.total] = weight * sigmoidf(p1 + b1);
-            out[2 * a.total] = weight * sigmoidf(p2 + b2);
-        }
-    }
-}
-
-__global__ void __launch_bounds__(256) sweep_fold_kernel(const float* __restrict__ products, const float* __restrict__ acc,
-                                                         long long num_rays, int samples, int views, int white_bkgd,
-                                                         float* __restrict__ out) {
-    const long long count = (long long)views * 3 * num_rays, total = num_rays * samples;
-    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < count; t += (long long)gridDim.x * 256) {
-        const long long vc = t / num_rays, ray = t - vc * num_rays;
-        const float* p = products + vc * total + ray * samples;
-        float sum = 0.0f;
-        for (int s = 0; s < samples; ++s) sum += p[s];
-        if (white_bkgd) sum += 1.0f - acc[ray];
-        const long long v = vc / 3;
-        out[(v * num_rays + ray) * 3 + (vc - 3 * v)] = sum;
-    }
+    sweep_tail<VT>(acc, head, a.u, a.products, sample, live, ray, weight, a.num_rays, a.total, a.views, h);
 }
 
 struct SweepPlan {
@@ -155,8 +78,6 @@ struct SweepPlan {
     long long wvt_floats = 0, u_floats = 0, product_floats = 0;
     long long total() const { return wvt_floats + u_floats + product_floats; }
 };
-
-long long round64(long long x) { return (x + 63) / 64 * 64; }
 
 int plan_sweep(const snerf_mlp_desc* desc, long long num_rays, int num_samples, int num_views, SweepPlan* out) {
     if (!desc) return snerf::fail(SNERF_E_INVALID, "view_sweep: NULL descriptor");
@@ -226,7 +147,7 @@ extern "C" int snerf_view_sweep(const snerf_mlp_desc* desc, const float* const* 
 
     hipLaunchKernelGGL(sweep_transpose_kernel, dim3((unsigned)((p.wvt_floats + 255) / 256)), dim3(256), 0, s, params[pv], ld, m.width,
                        m.views_width, wvt);
-    hipLaunchKernelGGL(sweep_view_bias_kernel, dim3((unsigned)(pairs < 65536 ? pairs : 65536)), dim3(64), 0, s, params[pv],
+    hipLaunchKernelGGL(sweep_view_bias_kernel<kSweepFp32>, dim3((unsigned)(pairs < 65536 ? pairs : 65536)), dim3(64), 0, s, params[pv],
                        params[pv + 1], ld, m.width, m.views_width, m.views_degree, view_dirs, pairs, u);
     SweepArgs a;
     a.acts = saved_acts; a.weights = weights; a.wvt = wvt; a.u = u; a.wo = params[pv + 2]; a.bo = params[pv + 3];

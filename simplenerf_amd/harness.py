@@ -203,22 +203,43 @@ def _sweep_levels(model):
     return [(0, model.coarse_model)] + ([(3, model.fine_model)] if model.fine_mlp_needed else [])
 
 
+# The 16-bit modes whose one-trunk-pass route is on by default: those measured at least 2 x faster than their plain loop at 16 views
+# of a 756 x 1008 frame.
+SWEEP_HALF_PRECISIONS = (ops.PRECISION_F16, ops.PRECISION_BF16, ops.PRECISION_F16S8, ops.PRECISION_BF16S8)
+
+
+def _sweep_workspace_query(model):
+    """The workspace query of the sweep that reads what ``model``'s precision keeps (None: no sweep does): ``snerf_view_sweep``
+    for fp32 activations, ``snerf_view_sweep_half`` for the 16-bit pieces of 'f16' / 'bf16' and their 8-bit variants.  'f16x3'
+    keeps fp32 tiles and stays on the plain loop."""
+    lib = _lib.load()
+    if model.precision == ops.PRECISION_FP32:
+        return lib.snerf_view_sweep_workspace_floats
+    if model.precision in SWEEP_HALF_PRECISIONS:
+        return lib.snerf_view_sweep_half_workspace_floats
+    return None
+
+
 def view_sweep_is_fast(model) -> bool:
-    """Whether ``predict_view_sweep`` takes the one-trunk-pass route for ``model``: an fp32 model whose displayed MLP is a shape
-    ``snerf_view_sweep`` is built for (the library decides: its workspace query is 0 for every other descriptor) and none of
-    whose MLPs predicts visibility."""
-    if not hasattr(model, 'coarse_model') or model.precision != ops.PRECISION_FP32:
+    """Whether ``predict_view_sweep`` takes the one-trunk-pass route for ``model``: an fp32, 'f16', 'bf16', 'f16s8' or 'bf16s8' model
+    whose displayed MLP is a shape its precision's sweep is built for (the library decides: the workspace query is 0 for every
+    other descriptor) and none of whose MLPs predicts visibility."""
+    if not hasattr(model, 'coarse_model'):
+        return False
+    query = _sweep_workspace_query(model)
+    if query is None:
         return False
     levels = _sweep_levels(model)
     if any(module.predict_visibility for _, module in levels):
         return False
     desc = ops.mlp_desc(levels[-1][1].mlp_configs)
-    return int(_lib.load().snerf_view_sweep_workspace_floats(ctypes.byref(desc), 1, 1, 1)) > 0
+    return int(query(ctypes.byref(desc), 1, 1, 1)) > 0
 
 
 def _sweep_ray_block(model, num_views: int) -> int:
     """Rays per block so that the saved activations of every level plus the sweep's scratch stay under SWEEP_ACTIVATION_BYTES
-    (8 x 256 at 64 + 128 samples: ~2.6 MB of activations per ray, so ~3000 rays)."""
+    (8 x 256 at 64 + 128 samples: ~2.6 MB of activations per ray, so ~3000 rays; the allocation is the same in the 16-bit modes,
+    whose pieces fill half of it)."""
     lib = _lib.load()
     mcfg = model.configs['model']
     s_c = int(mcfg['coarse_mlp']['num_samples'])
@@ -227,7 +248,7 @@ def _sweep_ray_block(model, num_views: int) -> int:
         samples = s_c + (int(mcfg['fine_mlp']['num_samples']) if level == 3 else 0)
         desc = ops.mlp_desc(module.mlp_configs)
         floats += int(lib.snerf_mlp_saved_floats(ctypes.byref(desc), 1024, samples))
-    floats += int(lib.snerf_view_sweep_workspace_floats(ctypes.byref(desc), 1024, samples, num_views))     # (the displayed level's)
+    floats += int(_sweep_workspace_query(model)(ctypes.byref(desc), 1024, samples, num_views))     # (the displayed level's)
     return max(32, int(SWEEP_ACTIVATION_BYTES * 1024 // (4 * floats)))
 
 
@@ -241,9 +262,10 @@ def predict_view_sweep(model, configs: dict, camera: dict, view_cameras, device,
     as ``retrieve_inference_outputs`` converts them.
 
     Fast route (``view_sweep_is_fast``): per block of ``ray_block`` rays ONE render that keeps the activations
-    (``ops.render_keep_activations``), ONE ``ops.view_sweep`` over all V cameras and one display conversion per view; everything up
+    (``ops.render_keep_activations`` at the model's precision), ONE ``ops.view_sweep`` (fp32) or ``ops.view_sweep_half`` ('f16',
+    'bf16' and their 8-bit variants) over all V cameras and one display conversion per view; everything up
     to the views layer's pre-activation is computed once, not V times.  ``ray_block`` defaults to what keeps a block's saved
-    activations and scratch under SWEEP_ACTIVATION_BYTES.  Every other model (other precisions, layered shapes, predict_visibility)
+    activations and scratch under SWEEP_ACTIVATION_BYTES.  Every other model ('f16x3', layered shapes, predict_visibility)
     takes the plain loop, one ordinary render per view camera (``frame_batch(view_camera=...)``, blocks of ``ray_block`` or 65536
     rays), with the answer in the same form."""
     view_cameras = list(view_cameras)
@@ -278,9 +300,14 @@ def predict_view_sweep(model, configs: dict, camera: dict, view_cameras, device,
             rays = min(block, n - first)
             kept = ops.render_keep_activations(packed, frame_batch(camera, ndc, device, first, rays), ndc, white, bool(mcfg['lindisp']),
                                                int(mcfg['coarse_mlp']['num_samples']),
-                                               int(mcfg['fine_mlp']['num_samples']) if shown_level == 3 else 0)
+                                               int(mcfg['fine_mlp']['num_samples']) if shown_level == 3 else 0,
+                                               precision=model.precision)
             dirs = torch.stack([view_directions(camera, view_camera, device, first, rays) for view_camera in view_cameras])
-            swept = ops.view_sweep(packed[shown_level], params, kept['saved_acts'], kept['weights'], kept['acc'], dirs, white)
+            if model.precision == ops.PRECISION_FP32:
+                swept = ops.view_sweep(packed[shown_level], params, kept['saved_acts'], kept['weights'], kept['acc'], dirs, white)
+            else:
+                swept = ops.view_sweep_half(packed[shown_level], params, kept['saved_acts'], kept['weights'], kept['acc'], dirs, white,
+                                            model.precision)
             rgb[:, first:first + rays] = swept
             for v in range(count):
                 images[v, first:first + rays] = ops.to_display(swept[v], None)[0]

@@ -492,14 +492,20 @@ class RenderCall:
 
 
 # ---------------------------------------------------------------------------------------------- view sweep
+SWEEP_BASE_PRECISION = {PRECISION_F16S8: PRECISION_F16, PRECISION_BF16S8: PRECISION_BF16}      # the 8-bit modes render as their base mode
+
+
 @torch.no_grad()
 def render_keep_activations(mlps: List[Optional['PackedMlp']], rays: Dict[str, Tensor], ndc: bool, white_bkgd: bool, lindisp: bool,
-                            num_coarse: int, num_fine: int, z_vals_fine: Optional[Tensor] = None) -> Dict[str, object]:
-    """One ``snerf_render_forward`` that keeps the activations without recording a backward: fp32, no jitter, no density noise.
-    ``mlps`` as ``RenderCall`` takes them, packed for the training layout (the storing forward reads it).  Returns, for the level a
+                            num_coarse: int, num_fine: int, z_vals_fine: Optional[Tensor] = None,
+                            precision: int = PRECISION_FP32) -> Dict[str, object]:
+    """One ``snerf_render_forward`` that keeps the activations without recording a backward: no jitter, no density noise.
+    ``mlps`` as ``RenderCall`` takes them, packed for the training layout at ``precision`` (the storing forward reads it).
+    ``precision``: 'f16s8' / 'bf16s8' run as 'f16' / 'bf16' -- their rendering is the base mode's bit for bit, and what a sweep
+    reads of the activations must not depend on how the 8-bit forwards keep their trunk tiles.  Returns, for the level a
     frame is displayed from (the fine MLP's, the coarse one's without a fine MLP): 'level', 'num_samples', 'saved_acts',
     'weights' (n,S), 'acc' (n,) and 'outputs', that level's per-ray outputs by name (rgb, acc, depth, depth_var, ...)."""
-    call = RenderCall(mlps, ndc, white_bkgd, lindisp, num_coarse, num_fine, PRECISION_FP32, keep_activations=True,
+    call = RenderCall(mlps, ndc, white_bkgd, lindisp, num_coarse, num_fine, SWEEP_BASE_PRECISION.get(precision, precision), keep_activations=True,
                       per_sample=('alpha', 'weights'))
     draws = {} if z_vals_fine is None else {'z_vals_fine': z_vals_fine}
     _, _, levels = call.forward(rays, draws)
@@ -534,6 +540,35 @@ def view_sweep(mlp: 'PackedMlp', params: List[Tensor], saved_acts: Tensor, weigh
     work = _workspace('view_sweep', dev, 4 * floats) if floats else None
     _enqueue('snerf_view_sweep', dev, ctypes.byref(mlp.desc), arr, len(held), _ptr(saved_acts), _ptr(weights), _ptr(acc),
              _ptr(view_dirs), n, s, v, int(bool(white_bkgd)), _ptr(out), _ptr(work))
+    return out
+
+
+def view_sweep_half(mlp: 'PackedMlp', params: List[Tensor], saved_acts: Tensor, weights: Tensor, acc: Optional[Tensor],
+                    view_dirs: Tensor, white_bkgd: bool = False, precision: int = PRECISION_BF16) -> Tensor:
+    """snerf_view_sweep_half (csrc/simplenerf_sweep16.h): ``view_sweep`` from the 16-bit activations a storing forward of ``mlp``
+    kept at ``precision`` (PRECISION_F16 or PRECISION_BF16; the 8-bit modes keep ``feature`` like their base mode and are mapped to
+    it), with the views layer's operands rounded to that format as the mode's own render rounds them."""
+    lib = _lib.load()
+    n, s = weights.shape
+    v = view_dirs.shape[0]
+    weights = _dev(weights, 'weights', (n, s))
+    acc = _dev(acc, 'acc', (n,)) if white_bkgd else None
+    view_dirs = _dev(view_dirs, 'view_dirs', (v, n, 3))
+    saved_acts = _dev(saved_acts, 'saved_acts')
+    dev = weights.device
+    need = int(lib.snerf_view_sweep_half_acts_floats(ctypes.byref(mlp.desc), n, s))
+    if saved_acts.numel() < need:
+        raise RuntimeError(f'saved_acts: {saved_acts.numel()} floats, the sweep of {n} rays x {s} samples of this MLP reads {need}')
+    if len(params) != mlp.num_params:
+        raise RuntimeError(f'expected {mlp.num_params} parameter tensors, got {len(params)}')
+    held = [_dev(p, f'param[{i}]') for i, p in enumerate(params)]
+    arr = (ctypes.c_void_p * len(held))(*[p.data_ptr() for p in held])
+    out = torch.empty((v, n, 3), dtype=torch.float32, device=dev)
+    floats = int(lib.snerf_view_sweep_half_workspace_floats(ctypes.byref(mlp.desc), n, s, v))
+    work = _workspace('view_sweep_half', dev, 4 * floats) if floats else None
+    precision = SWEEP_BASE_PRECISION.get(int(precision), int(precision))
+    _enqueue('snerf_view_sweep_half', dev, ctypes.byref(mlp.desc), arr, len(held), _ptr(saved_acts), _ptr(weights), _ptr(acc),
+             _ptr(view_dirs), n, s, v, int(bool(white_bkgd)), precision, _ptr(out), _ptr(work))
     return out
 
 

@@ -1,15 +1,17 @@
 #!/usr/bin/env python3
 """Time the static-camera view sweep against the loop it replaces.  A record, not a gate (needs the GPU).
 
-    python tools/measure_view_sweep.py [--views 16] [--repeats 3] [--resolution 756 1008] [--out FILE]     -> one JSON line
+    python tools/measure_view_sweep.py [--views 16] [--repeats 3] [--resolution 756 1008] [--precision fp32] [--out FILE]
+                                                                                                            -> one JSON line
 
-One fern frame (756 x 1008), 64 + 128 samples, 8 x 256 coarse + fine, fp32, V view cameras scattered around the frame's own:
+One fern frame (756 x 1008), 64 + 128 samples, 8 x 256 coarse + fine, V view cameras scattered around the frame's own, at
+``--precision`` (fp32, f16, bf16, f16s8 or bf16s8: a mode with a one-trunk-pass route):
   sweep_ms     ``harness.predict_view_sweep`` on its fast route (default ray block), HIP events around the whole call
   parts_ms     the same block loop with events around its three parts, summed over the blocks: the keep-activations render,
-               ``ops.view_sweep``, the display conversions (the parts add up to less than the sweep: ray generation, the copies into
+               ``ops.view_sweep`` (``ops.view_sweep_half`` in the 16-bit modes), the display conversions (the parts add up to less than the sweep: ray generation, the copies into
                the frame buffers and the copy of the images to the host are outside them)
-  loop_ms      V ordinary renders of the frame (``harness.predict_frame(view_camera=...)``): what the fallback route, and the code
-               before the sweep existed, needs
+  loop_ms      V ordinary renders of the frame at the same precision (``harness.predict_frame(view_camera=...)``): what the
+               fallback route, and the code before the mode's sweep existed, needs
   ratio        loop_ms / sweep_ms
 Each figure is the median of ``repeats`` runs after one warm run; the spread (min, max) is recorded beside it."""
 import argparse
@@ -56,9 +58,13 @@ def sweep_parts(model, configs, camera, view_cameras, block):
         dirs = torch.stack([harness.view_directions(camera, c, DEV, first, rays) for c in view_cameras])
         events = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         events[0].record()
-        kept = ops.render_keep_activations(packed, batch, True, False, False, mcfg['coarse_mlp']['num_samples'], mcfg['fine_mlp']['num_samples'])
+        kept = ops.render_keep_activations(packed, batch, True, False, False, mcfg['coarse_mlp']['num_samples'], mcfg['fine_mlp']['num_samples'],
+                                           precision=model.precision)
         events[1].record()
-        swept = ops.view_sweep(packed[3], params, kept['saved_acts'], kept['weights'], kept['acc'], dirs, False)
+        if model.precision == ops.PRECISION_FP32:
+            swept = ops.view_sweep(packed[3], params, kept['saved_acts'], kept['weights'], kept['acc'], dirs, False)
+        else:
+            swept = ops.view_sweep_half(packed[3], params, kept['saved_acts'], kept['weights'], kept['acc'], dirs, False, model.precision)
         events[2].record()
         for v in range(len(view_cameras)):
             ops.to_display(swept[v], None)
@@ -76,10 +82,11 @@ def main():
     parser.add_argument('--views', type=int, default=16)
     parser.add_argument('--repeats', type=int, default=3)
     parser.add_argument('--resolution', type=int, nargs=2, default=None)
+    parser.add_argument('--precision', default='fp32', choices=['fp32', 'f16', 'bf16', 'f16s8', 'bf16s8'])
     parser.add_argument('--out', default=None)
     args = parser.parse_args()
 
-    configs = synth.with_overrides(synth.make_configs('config2'), hip_precision='fp32')
+    configs = synth.with_overrides(synth.make_configs('config2'), hip_precision=args.precision)
     model = get_model(configs, None)
     shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
     model.load_state_dict({k: torch.from_numpy(v) for k, v in synth.synth_state_dict(shapes, 0, sigma_gain=60.0).items()})
@@ -102,7 +109,7 @@ def main():
     sweep_parts(model, configs, camera, view_cameras, block)
     parts = [sweep_parts(model, configs, camera, view_cameras, block) for _ in range(args.repeats)]
     record = {'what': 'static-camera view sweep against V ordinary renders of the frame', 'device': torch.cuda.get_device_name(0),
-              'resolution': list(camera['resolution']), 'samples': [64, 128], 'mlp': '8x256 / 1x128, fp32', 'views': args.views,
+              'resolution': list(camera['resolution']), 'samples': [64, 128], 'mlp': f'8x256 / 1x128, {args.precision}', 'precision': args.precision, 'views': args.views,
               'repeats': args.repeats, 'ray_block': block, 'sweep_ms': sweep, 'loop_ms': loop,
               'parts_ms': {name: statistics.median(p[name] for p in parts) for name in parts[0]},
               'ratio': loop['median'] / sweep['median']}
