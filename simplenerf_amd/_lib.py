@@ -15,7 +15,7 @@ from .build import INCLUDE
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libsimplenerf_hip.so')
 
-# The headers are the binding's only source (the two under include/, then ADDED_HEADERS, SWEEP_HEADERS and SWEEP16_HEADERS below): every prototype, struct layout, #define and enumerator below is read from them
+# The headers are the binding's only source (the two under include/, then ADDED_HEADERS, SWEEP_HEADERS, SWEEP16_HEADERS and PNG_HEADERS below): every prototype, struct layout, #define and enumerator below is read from them
 # (_cdecl.py), in inclusion order.  snerf_iteration records live in pinned host and device memory and are passed by address.
 HEADERS = ('simplenerf_hip.h', 'simplenerf_train.h')
 _decls = _cdecl.Header(by_address=('snerf_iteration',))
@@ -46,6 +46,14 @@ for _name in SWEEP16_HEADERS:
         _decls.read(_f.read(), os.path.basename(_name))
 SWEEP16_SIGNATURES = {_name: _sig for _name, _sig in _decls.functions.items()
                       if _name not in SIGNATURES and _name not in ADDED_SIGNATURES and _name not in SWEEP_SIGNATURES}
+# The PNG frame encoder (csrc/simplenerf_png.h): a fifth group, read after the others and bound with them.
+PNG_HEADERS = (os.path.join(_HERE, 'csrc', 'simplenerf_png.h'),)
+_earlier = set(_decls.functions)
+for _name in PNG_HEADERS:
+    with open(_name) as _f:
+        _decls.read(_f.read(), os.path.basename(_name))
+PNG_SIGNATURES = {_name: _sig for _name, _sig in _decls.functions.items() if _name not in _earlier}
+C = types.SimpleNamespace(**_decls.constants)      # (again: with the #defines of the headers read after the first two)
 ABI_VERSION = C.SNERF_ABI_VERSION
 RENDER_LEVELS, CAMERA_FLOATS = C.SNERF_RENDER_LEVELS, C.SNERF_CAMERA_FLOATS
 LOSS_MAX_TERMS, LOSS_MAX_GROUPS = C.SNERF_LOSS_MAX_TERMS, C.SNERF_LOSS_MAX_GROUPS
@@ -72,7 +80,8 @@ def load() -> ctypes.CDLL:
     # device pointers, streams and the primary context are shared with torch's allocator.
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**SIGNATURES, **ADDED_SIGNATURES, **SWEEP_SIGNATURES, **SWEEP16_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **ADDED_SIGNATURES, **SWEEP_SIGNATURES, **SWEEP16_SIGNATURES,
+                                      **PNG_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

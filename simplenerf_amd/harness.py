@@ -253,7 +253,8 @@ def _sweep_ray_block(model, num_views: int) -> int:
 
 
 @torch.no_grad()
-def predict_view_sweep(model, configs: dict, camera: dict, view_cameras, device, ray_block: Optional[int] = None) -> dict:
+def predict_view_sweep(model, configs: dict, camera: dict, view_cameras, device, ray_block: Optional[int] = None,
+                       keep_device_images: bool = False) -> dict:
     """``camera``'s frame under the view directions of each of ``view_cameras`` (dicts like ``camera``): the eval-mode render of
     the reference's static-camera video (src/Tester01.py start_testing with ``extrinsic_viewcam``), on one rank.
 
@@ -267,7 +268,8 @@ def predict_view_sweep(model, configs: dict, camera: dict, view_cameras, device,
     to the views layer's pre-activation is computed once, not V times.  ``ray_block`` defaults to what keeps a block's saved
     activations and scratch under SWEEP_ACTIVATION_BYTES.  Every other model ('f16x3', layered shapes, predict_visibility)
     takes the plain loop, one ordinary render per view camera (``frame_batch(view_camera=...)``, blocks of ``ray_block`` or 65536
-    rays), with the answer in the same form."""
+    rays), with the answer in the same form.  ``keep_device_images``: also 'images_device', the (V,h,w,3) uint8 frames as the
+    tensor they were converted into."""
     view_cameras = list(view_cameras)
     h, w = int(camera['resolution'][0]), int(camera['resolution'][1])
     n, count = h * w, len(view_cameras)
@@ -314,17 +316,29 @@ def predict_view_sweep(model, configs: dict, camera: dict, view_cameras, device,
             for name in map_names:
                 maps[name][first:first + rays] = ops.to_display(None, kept['outputs'][name], colour=False)[1]
     out = {'images': images.reshape(count, h, w, 3).cpu().numpy(), 'rgb': rgb}
+    if keep_device_images:
+        out['images_device'] = images.reshape(count, h, w, 3)
     out.update({name: value.reshape(h, w).cpu().numpy() for name, value in maps.items()})
     return out
 
 
-def save_static_camera_frames(model, configs: dict, preprocessor, extrinsics, out_dirpath, device) -> dict:
+def save_static_camera_frames(model, configs: dict, preprocessor, extrinsics, out_dirpath, device, png_encoder: str = 'host') -> dict:
     """The frames of the reference's StaticCameraVideo (start_testing_static_videos + Tester.start_testing): ``extrinsics`` (N,4,4)
     raw poses; the frame of ``extrinsics[0]`` under the view cameras ``extrinsics[1:]`` (``predict_view_sweep``), written as
-    ``predicted_frames/{i:04}.png`` for i = 0 .. N-2 under ``out_dirpath``.  The mp4 is not written.  Returns the sweep's result."""
+    ``predicted_frames/{i:04}.png`` for i = 0 .. N-2 under ``out_dirpath``.  The mp4 is not written.  Returns the sweep's result.
+    ``png_encoder='device'``: all N-1 frames are encoded on the device in one ``png_files`` call."""
     import os
+    on_device = _check_png_encoder(png_encoder)
     cameras = [preprocessor.camera(pose) for pose in extrinsics]
-    result = predict_view_sweep(model, configs, cameras[0], cameras[1:], device)
+    result = predict_view_sweep(model, configs, cameras[0], cameras[1:], device, keep_device_images=on_device)
+    if on_device:
+        frames = result.pop('images_device')
+        directory = os.path.join(os.fspath(out_dirpath), 'predicted_frames')
+        os.makedirs(directory, exist_ok=True)
+        for i, data in enumerate(png_files(frames) if frames.shape[0] else []):
+            with open(os.path.join(directory, f'{i:04}.png'), 'wb') as f:
+                f.write(data)
+        return result
     for i, image in enumerate(result['images']):
         save_image(os.path.join(os.fspath(out_dirpath), 'predicted_frames', f'{i:04}.png'), image)
     return result
@@ -777,20 +791,63 @@ def _png_bytes(array) -> bytes:
         raise RuntimeError(f'PNG writer takes uint8 (h,w) or (h,w,3) arrays, got {a.dtype} {a.shape}')
     h, w = a.shape[:2]
     rows = numpy.concatenate([numpy.zeros((h, 1), dtype=numpy.uint8), a.reshape(h, -1)], axis=1)   # filter type 0 per row
+    return _png_container(zlib.compress(rows.tobytes(), 6), h, w, a.ndim == 3)
+
+
+def _png_container(stream: bytes, h: int, w: int, colour: bool) -> bytes:
+    """The file around the zlib stream of an 8-bit grey or RGB image's filtered rows: signature, IHDR, one IDAT, IEND."""
+    import struct
+    import zlib
 
     def chunk(tag: bytes, data: bytes) -> bytes:
         return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xFFFFFFFF)
 
-    header = struct.pack('>IIBBBBB', w, h, 8, 2 if a.ndim == 3 else 0, 0, 0, 0)
-    return b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', header) + chunk(b'IDAT', zlib.compress(rows.tobytes(), 6)) + chunk(b'IEND', b'')
+    header = struct.pack('>IIBBBBB', w, h, 8, 2 if colour else 0, 0, 0, 0)
+    return b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', header) + chunk(b'IDAT', stream) + chunk(b'IEND', b'')
 
 
-def save_image(path, image) -> None:
-    """``image``: uint8 (h,w,3) array or tensor (e.g. ``to_display`` output reshaped); ``.png`` or ``.npy`` by suffix."""
+PNG_ENCODERS = ('host', 'device')      # 'host': _png_bytes (filter type 0, zlib level 6, one host thread); 'device': png_files
+
+
+def _check_png_encoder(png_encoder) -> bool:
+    """True for 'device'; any value but the two names raises."""
+    if png_encoder not in PNG_ENCODERS:
+        raise RuntimeError(f"png_encoder: expected 'host' or 'device', got {png_encoder!r}")
+    return png_encoder == 'device'
+
+
+def _device_u8(value, what: str) -> Tensor:
+    if not isinstance(value, torch.Tensor) or not value.is_cuda:
+        raise RuntimeError(f"{what}: png_encoder='device' encodes tensors that are on the device, got "
+                           f"{type(value).__name__}{' on ' + str(value.device) if isinstance(value, torch.Tensor) else ''}; "
+                           f"there is no fall-back to the host writer")
+    return value
+
+
+def png_files(images) -> list:
+    """The PNG files of ``images`` -- uint8 (K,h,w) grey or (K,h,w,3) RGB on the device -- as K ``bytes``, encoded there: one
+    ``ops.png_deflate`` call for all K (adaptive row filters, run-length tokens, one Huffman block per 32 KiB), one copy of the K
+    stream lengths to the host, then one copy per stream of exactly its bytes; the container around each stream is ``_png_bytes``'
+    (signature, IHDR, one IDAT, IEND; the CRC-32 on the host).  The files decode to the pixels ``_png_bytes`` would store; the bytes
+    differ (other filters, another deflate)."""
+    images = _device_u8(images, 'png_files')
+    streams, sizes = ops.png_deflate(images)
+    h, w = int(images.shape[1]), int(images.shape[2])
+    return [_png_container(streams[i, :n].cpu().numpy().tobytes(), h, w, images.dim() == 4) for i, n in enumerate(sizes.cpu().tolist())]
+
+
+def save_image(path, image, png_encoder: str = 'host') -> None:
+    """``image``: uint8 (h,w,3) array or tensor (e.g. ``to_display`` output reshaped); ``.png`` or ``.npy`` by suffix.
+    ``png_encoder='device'``: a ``.png`` of a tensor on the device is encoded there (``png_files``)."""
     import os
     import numpy
     path = os.fspath(path)
     os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+    if _check_png_encoder(png_encoder) and path.endswith('.png'):
+        data, = png_files(_device_u8(image, 'save_image')[None])
+        with open(path, 'wb') as f:
+            f.write(data)
+        return
     array = image.cpu().numpy() if isinstance(image, torch.Tensor) else numpy.asarray(image)
     if path.endswith('.png'):
         with open(path, 'wb') as f:
@@ -801,29 +858,39 @@ def save_image(path, image) -> None:
         raise RuntimeError(f'Unknown image format: {path}')
 
 
-def save_depth(path, depth, as_png: bool = False) -> None:
+def save_depth(path, depth, as_png: bool = False, png_encoder: str = 'host') -> None:
     """``depth``: float (h,w); ``.npy`` keeps the values (plus a PNG preview when ``as_png``), ``.png`` stores
     round(depth / depth.max() * 255) like the reference (src/Tester01.py:80-92).  A float32 tensor on the device is converted
-    there (``ops.maps_to_u8``: the same bytes) and its preview copied as one byte per pixel."""
+    there (``ops.maps_to_u8``: the same bytes) and its preview copied as one byte per pixel -- or, with ``png_encoder='device'``,
+    encoded there as well (``png_files``; the depth must be such a tensor)."""
     import os
     import numpy
     path = os.fspath(path)
     os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+    on_device = _check_png_encoder(png_encoder)
+    if on_device and (_device_u8(depth, 'save_depth').dtype != torch.float32 or depth.dim() != 2):
+        raise RuntimeError(f"save_depth: png_encoder='device' takes a float32 (h,w) tensor, got {depth.dtype} {tuple(depth.shape)}")
     if isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32:
         # the preview on the device (snerf_maps_to_u8): one byte per pixel crosses, and the floats only for a .npy
-        preview = ops.maps_to_u8(depth.reshape(1, -1), (ops.MAP_SCALE_MAX,))[0].reshape(depth.shape).cpu().numpy()
+        preview = ops.maps_to_u8(depth.reshape(1, -1), (ops.MAP_SCALE_MAX,))[0].reshape(depth.shape)
+        if not on_device:
+            preview = preview.cpu().numpy()
         array = depth.cpu().numpy() if path.endswith('.npy') else None
     else:
         array = depth.cpu().numpy() if isinstance(depth, torch.Tensor) else numpy.asarray(depth)
         preview = numpy.round(array / array.max() * 255).astype('uint8')
+
+    def preview_file() -> bytes:
+        return png_files(preview[None])[0] if on_device else _png_bytes(preview)
+
     if path.endswith('.png'):
         with open(path, 'wb') as f:
-            f.write(_png_bytes(preview))
+            f.write(preview_file())
     elif path.endswith('.npy'):
         numpy.save(path, array)
         if as_png:
             with open(os.path.splitext(path)[0] + '.png', 'wb') as f:
-                f.write(_png_bytes(preview))
+                f.write(preview_file())
     else:
         raise RuntimeError(f'Unknown depth format: {path}')
 
@@ -901,10 +968,12 @@ def _validation_maps(outputs: dict, losses: Optional[dict], frame_num, frame_num
     return maps
 
 
-def _convert_and_write(maps, resolution, frame_num, save_dirpath, keep, write_floats: bool = True) -> None:
+def _convert_and_write(maps, resolution, frame_num, save_dirpath, keep, write_floats: bool = True, png_encoder: str = 'host') -> None:
     """All maps of a frame through ONE ``ops.maps_to_u8`` call -- the colour as rows of mode 0 (save_image :384-387), every other map
     with mode 1 (save_numpy_array :397-409) -- then the reference's files: a PNG for the colour, ``.npy`` + PNG for the rest
-    (``write_floats`` False: the PNG only, as save_sample_images writes)."""
+    (``write_floats`` False: the PNG only, as save_sample_images writes).  ``png_encoder='device'``: the PNGs are encoded on the
+    device, the frame's colour images in one ``png_files`` call and all its grey maps in a second; the 8-bit maps cross to the host
+    only for ``keep``."""
     import os
     import numpy
     h, w = int(resolution[0]), int(resolution[1])
@@ -917,12 +986,21 @@ def _convert_and_write(maps, resolution, frame_num, save_dirpath, keep, write_fl
         spans.append((len(modes), flat.numel() // n))
         rows.append(flat)
         modes += [ops.MAP_SCALE_255 if colour else ops.MAP_SCALE_MAX] * (flat.numel() // n)
+    on_device = _check_png_encoder(png_encoder)
     floats = torch.cat(rows).reshape(len(modes), n)
-    bytes_host = ops.maps_to_u8(floats, modes)[0].cpu().numpy()
+    bytes_device = ops.maps_to_u8(floats, modes)[0]
+    bytes_host = bytes_device.cpu().numpy() if keep is not None or not on_device else None
+    encoded = {}
+    if on_device and save_dirpath is not None:
+        for colour in (True, False):
+            group = [(stem, first, count) for (stem, _, c), (first, count) in zip(maps, spans) if c == colour]
+            if group:
+                stack = torch.stack([bytes_device[first:first + count].reshape((h, w, 3) if colour else (h, w)) for _, first, count in group])
+                encoded.update(zip((stem for stem, _, _ in group), png_files(stack)))
     floats_host = floats.cpu().numpy() if keep is not None or (save_dirpath is not None and write_floats) else None
     for (stem, _, colour), (first, count) in zip(maps, spans):
         shape = (h, w, 3) if colour else (h, w)
-        as_u8 = bytes_host[first:first + count].reshape(shape)
+        as_u8 = None if bytes_host is None else bytes_host[first:first + count].reshape(shape)
         as_float = None if floats_host is None else floats_host[first:first + count].reshape(shape)
         if keep is not None:
             keep[(frame_num, stem)] = {'float': as_float, 'u8': as_u8}
@@ -932,11 +1010,11 @@ def _convert_and_write(maps, resolution, frame_num, save_dirpath, keep, write_fl
             if not colour and write_floats:
                 numpy.save(path + '.npy', as_float)
             with open(path + '.png', 'wb') as f:
-                f.write(_png_bytes(as_u8))
+                f.write(encoded[stem] if on_device else _png_bytes(as_u8))
 
 
 def run_validation(model, loss_computer, data_preprocessor, iter_num: int, configs: dict, save_dirpath=None,
-                   keep: Optional[dict] = None) -> Dict[str, float]:
+                   keep: Optional[dict] = None, png_encoder: str = 'host') -> Dict[str, float]:
     """Trainer.run_validation (src/Trainer01.py:109-263) over every view of ``data_preprocessor`` (a train- or validation-mode
     DataPreprocessor), on one rank: the model goes to eval mode (:184) and back to train mode at the end (:262); every frame's
     ``get_next_batch(iter_num, frame_num)`` is cut into chunks of ``configs['validation_chunk_size']``, each chunk rendered under
@@ -949,13 +1027,15 @@ def run_validation(model, loss_computer, data_preprocessor, iter_num: int, confi
     and ``.npy`` + ``.png`` under ``predicted_depths/``, ``predicted_depths_variance/`` (with ``_ndc`` forms), ``predicted_visibilities/``
     and ``Losses/`` -- the 8-bit images from one ``ops.maps_to_u8`` call per frame, written by this module's PNG writer.
     ``keep``: a dict that receives ``{(frame_num, file name without suffix, relative to save_dirpath): {'float': array, 'u8': array}}``
-    for the same arrays, with or without a directory.
+    for the same arrays, with or without a directory.  ``png_encoder='device'``: the PNGs are encoded on the device (``png_files``: per
+    frame one call for its colour images and one for its grey maps) -- the same file names, the same pixels, other bytes.
 
     A loss list that reads outputs an eval-mode model does not produce fails here as it does in the reference: the augmentation
     models run in training mode only (src/models/SimpleNeRF01.py:170, :186), so PointsAugmentationDepthLoss02 and its siblings index
     a missing key -- every shipped experiment sets ``validation_interval`` beyond ``num_iterations`` (NerfLlffTrainerTester01.py
     :438-441).  A loss whose result carries no ``loss_maps`` (the SparseDepthMSE family) fails with ``validation_save_loss_maps``
     as at :256; CoarseFineConsistencyLoss02 needs ``common_data``, which held-out views do not carry."""
+    _check_png_encoder(png_encoder)
     resolution = data_preprocessor.preprocessed_data_dict['nerf_data']['resolution']
     chunk_size = int(configs['validation_chunk_size'])
     with_maps = bool(configs['validation_save_loss_maps'])
@@ -981,20 +1061,23 @@ def run_validation(model, loss_computer, data_preprocessor, iter_num: int, confi
             totals[name] += value
         if save_dirpath is not None or keep is not None:
             maps = _validation_maps(frame_outputs, frame_losses if with_maps else None, frame_num, frame_nums, iter_label)
-            _convert_and_write(maps, resolution, frame_num, save_dirpath, keep)
+            _convert_and_write(maps, resolution, frame_num, save_dirpath, keep, png_encoder=png_encoder)
     model.train()
     return {name: value / len(frame_nums) for name, value in (totals or {}).items()}
 
 
-def save_sample_images(model, configs: dict, preprocessors, iter_num: int, save_dirpath, keep: Optional[dict] = None) -> None:
+def save_sample_images(model, configs: dict, preprocessors, iter_num: int, save_dirpath, keep: Optional[dict] = None,
+                       png_encoder: str = 'host') -> None:
     """Trainer.save_sample_images (:319-350): every view of every preprocessor in ``preprocessors`` (the reference's pair: train,
     validation) rendered from its stored processed pose -- ``create_test_data(pose, preprocess_pose=False)`` of the FIRST
     preprocessor, the model under no_grad in eval mode, the outputs of ``retrieve_inference_outputs`` (8-bit colour, depths clipped
     at 0; ``display_outputs``: they stay on the device) -- and written as PNGs: ``predicted_frames/<frame>_Iter<n>.png``,
     ``predicted_depths[_variance]/<frame>[_ndc]_Iter<n>.png``.  The depth previews come from one ``ops.maps_to_u8`` call per frame, so a
-    frame crosses to the host as bytes.  ``keep`` as in ``run_validation`` (the colour has no 'float' entry)."""
+    frame crosses to the host as bytes.  ``keep`` as in ``run_validation`` (the colour has no 'float' entry).
+    ``png_encoder='device'``: the PNGs are encoded on the device (``png_files``), the frame crosses as the bytes of its files."""
     import os
     import numpy
+    on_device = _check_png_encoder(png_encoder)
     first = preprocessors[0]
     resolution = first.get_model_configs()['resolution']
     iter_label = f'Iter{iter_num:05}'
@@ -1011,10 +1094,10 @@ def save_sample_images(model, configs: dict, preprocessors, iter_num: int, save_
                      (f'predicted_depths_variance/{frame_num:04}_{iter_label}', 'depth_var'),
                      (f'predicted_depths_variance/{frame_num:04}_ndc_{iter_label}', 'depth_var_ndc')]
             maps = [(stem, predictions[name], False) for stem, name in names if name in predictions]
-            _convert_and_write(maps, resolution, frame_num, save_dirpath, keep, write_floats=False)
+            _convert_and_write(maps, resolution, frame_num, save_dirpath, keep, write_floats=False, png_encoder=png_encoder)
             stem = f'predicted_frames/{frame_num:04}_{iter_label}'
-            image = predictions['image'].cpu().numpy()
+            image = predictions['image'].cpu().numpy() if keep is not None or not on_device else None
             if keep is not None:
                 keep[(frame_num, stem)] = {'u8': image}
-            save_image(os.path.join(os.fspath(save_dirpath), stem + '.png'), image)
+            save_image(os.path.join(os.fspath(save_dirpath), stem + '.png'), predictions['image'] if on_device else image, png_encoder)
     model.train()

@@ -692,6 +692,30 @@ def maps_to_u8(maps: Tensor, modes):
     return out, status
 
 
+PNG_FILTER_ADAPTIVE = C.SNERF_PNG_FILTER_ADAPTIVE      # filter_mode of snerf_png_deflate: the cheapest type per row; 0..4: that type on every row
+
+
+def png_deflate(images: Tensor, filter_mode: int = PNG_FILTER_ADAPTIVE):
+    """-> (streams uint8 (K, bound), sizes int64 (K)) on the device for ``images`` uint8 (K, h, w) grey or (K, h, w, 3) RGB on the
+    device: ``streams[i, :sizes[i]]`` is the complete zlib stream of frame i's IDAT chunk -- PNG row filtering (``filter_mode``),
+    run-length tokens and one dynamic Huffman block per 32 KiB of filtered bytes (csrc/simplenerf_png.h has the contract).  The PNG
+    container around a stream is the caller's (``harness.png_files``).  All K frames go through one call of four launches."""
+    images = _typed(images, 'images', (torch.uint8,))
+    if images.dim() not in (3, 4) or (images.dim() == 4 and images.shape[3] != 3):
+        raise RuntimeError(f'images: expected shape (K, h, w) or (K, h, w, 3), got {tuple(images.shape)}')
+    count, h, w = (int(v) for v in images.shape[:3])
+    channels = 3 if images.dim() == 4 else 1
+    dev, lib = images.device, _lib.load()
+    bound = int(lib.snerf_png_deflate_bound_bytes(h, w, channels))
+    streams = torch.empty((count, bound), dtype=torch.uint8, device=dev)
+    sizes = torch.zeros((count,), dtype=torch.int64, device=dev)
+    workspace = _workspace('png', dev, int(lib.snerf_png_deflate_workspace_bytes(count, h, w, channels))) if count and bound else None
+    # (an image the library does not take -- an empty one, 2 GiB of rows -- has bound 0 and no workspace: the call names the reason)
+    _enqueue('snerf_png_deflate', dev, _ptr(images), count, h, w, channels, int(filter_mode), _ptr(streams), _ptr(sizes),
+             _ptr(workspace))
+    return streams, sizes
+
+
 # ---------------------------------------------------------------------------------------------- Q1 frame metrics
 def _typed(t, name: str, dtypes, shape=None) -> Tensor:
     """Validate a device operand of one of ``dtypes`` (the metric inputs are uint8 / bool / float32); contiguous on return."""
