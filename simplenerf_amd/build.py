@@ -122,7 +122,7 @@ TORCH_EXT = os.path.join(TORCH_EXT_DIR, 'build', TORCH_EXT_NAME + '.so')
 
 
 def build_torch_extension(force: bool = False, verbose: bool = False) -> str:
-    """The TORCH_LIBRARY binding (csrc_torch/snerf_torch.cpp: torch.ops.snerf.render + its C++ autograd node) through
+    """The TORCH_LIBRARY binding (csrc_torch/snerf_torch.cpp: torch.ops.snerf.render + its C++ autograd node, snerf.jpeg_scan) through
     torch.utils.cpp_extension, in-tree: simplenerf_amd/csrc_torch/build/snerf_torch_ext.so.  Host compiler only -- the file is
     glue over the C ABI and links against libsimplenerf_hip.so ($ORIGIN-relative rpath), which must exist first."""
     import torch
@@ -130,7 +130,7 @@ def build_torch_extension(force: bool = False, verbose: bool = False) -> str:
     if not os.path.exists(LIB):
         raise RuntimeError(f'{LIB} must be built first (build_library)')
     source = os.path.join(TORCH_EXT_DIR, 'snerf_torch.cpp')
-    deps = [source, os.path.join(INCLUDE, 'simplenerf_hip.h')]
+    deps = [source, os.path.join(INCLUDE, 'simplenerf_hip.h'), os.path.join(CSRC, 'simplenerf_jpeg.h')]
     if not force and not _stale(TORCH_EXT, deps):
         return TORCH_EXT
     build_dir = os.path.dirname(TORCH_EXT)
@@ -139,7 +139,7 @@ def build_torch_extension(force: bool = False, verbose: bool = False) -> str:
     cpp_extension.load(
         name=TORCH_EXT_NAME, sources=[source], build_directory=build_dir, is_python_module=False, verbose=verbose,
         extra_cflags=['-O2', '-std=c++17', '-D__HIP_PLATFORM_AMD__', '-Wno-unused-function'],
-        extra_include_paths=[INCLUDE, os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'include')],
+        extra_include_paths=[INCLUDE, CSRC, os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'include')],
         extra_ldflags=[f'-L{torch_lib}', '-lc10_hip', '-ltorch_hip', f'-L{HERE}', '-lsimplenerf_hip', "-Wl,-rpath,'$$ORIGIN/../..'"])
     # (cpp_extension.load has also loaded it into this process: torch.ops.snerf exists from here on)
     if not os.path.exists(TORCH_EXT):

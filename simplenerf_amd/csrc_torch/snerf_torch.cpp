@@ -20,11 +20,14 @@
 #include <torch/custom_class.h>
 #include <torch/library.h>
 
+#include <climits>
 #include <memory>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "simplenerf_hip.h"
+#include "simplenerf_jpeg.h"
 
 namespace {
 
@@ -334,6 +337,31 @@ std::vector<Tensor> render(at::IntArrayRef cfg, at::IntArrayRef descs, const c10
     return RenderFunction::apply(params, call, cfg.vec(), descs.vec(), packed, rays, draws, keep_activations);
 }
 
+// snerf::jpeg_scan(images, quality) -> (scans uint8 (K, bound), scan_bytes int64 (K)): snerf_jpeg_scan (csrc/simplenerf_jpeg.h) on
+// uint8 (K, h, w) grey or (K, h, w, 3) RGB frames that are on the device; the same validation as ops.jpeg_scan's ctypes path.
+std::tuple<Tensor, Tensor> jpeg_scan(const Tensor& images, int64_t quality) {
+    TORCH_CHECK(images.is_cuda(), "images: expected a tensor on the GPU (the HIP renderer has no CPU path), got one on ", images.device());
+    TORCH_CHECK(images.scalar_type() == at::kByte, "images: expected uint8, got ", images.scalar_type());
+    TORCH_CHECK(images.dim() == 3 || (images.dim() == 4 && images.size(3) == 3), "images: expected shape (K, h, w) or (K, h, w, 3), got ",
+                images.sizes());
+    TORCH_CHECK(quality >= INT_MIN && quality <= INT_MAX && images.size(1) <= INT_MAX && images.size(2) <= INT_MAX && images.size(0) <= INT_MAX,
+                "images: a size or the quality does not fit an int");
+    const Tensor pixels = images.detach().contiguous();
+    const int count = (int)pixels.size(0), h = (int)pixels.size(1), w = (int)pixels.size(2), channels = pixels.dim() == 4 ? 3 : 1;
+    const int64_t bound = (int64_t)snerf_jpeg_scan_bound_bytes(h, w, channels);
+    Tensor scans = at::empty({count, bound}, pixels.options());
+    Tensor sizes = at::zeros({count}, pixels.options().dtype(at::kLong));
+    Tensor work;
+    if (count && bound) work = at::empty({(int64_t)snerf_jpeg_scan_workspace_bytes(count, h, w, channels)}, pixels.options());
+    // (an image the library does not take has bound 0 and no workspace: the call names the reason)
+    const c10::hip::HIPGuard guard(pixels.device().index());
+    hipStream_t stream = c10::hip::getCurrentHIPStream(pixels.device().index()).stream();
+    check_status(snerf_jpeg_scan(pixels.data_ptr<uint8_t>(), count, h, w, channels, (int)quality, scans.data_ptr<uint8_t>(),
+                                 reinterpret_cast<long long*>(sizes.data_ptr<int64_t>()), work.defined() ? work.data_ptr() : nullptr, stream),
+                 "snerf_jpeg_scan");
+    return {scans, sizes};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(snerf, m) {
@@ -341,8 +369,14 @@ TORCH_LIBRARY(snerf, m) {
     m.def("render(int[] cfg, int[] descs, Tensor?[] packed, Tensor?[] rays, Tensor?[] draws, Tensor[] params, int[] num_params, "
           "bool keep_activations, bool return_param_grads) -> Tensor[]");
     m.def("abi_version() -> int", []() -> int64_t { return snerf_abi_version(); });
+    m.def("jpeg_scan(Tensor images, int quality) -> (Tensor, Tensor)");
 }
 // One kernel for the autograd AND the backend key: the function builds its own graph node when gradients are recorded and
 // is a plain forward otherwise (no_grad, inference mode); it never re-dispatches.  (ROCm tensors carry the CUDA keys.)
 TORCH_LIBRARY_IMPL(snerf, Autograd, m) { m.impl("render", render); }
-TORCH_LIBRARY_IMPL(snerf, CUDA, m) { m.impl("render", render); }
+TORCH_LIBRARY_IMPL(snerf, CUDA, m) {
+    m.impl("render", render);
+    m.impl("jpeg_scan", jpeg_scan);
+}
+// (a tensor that is not on the device reaches the same function and its refusal)
+TORCH_LIBRARY_IMPL(snerf, CPU, m) { m.impl("jpeg_scan", jpeg_scan); }

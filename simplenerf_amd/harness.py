@@ -896,6 +896,175 @@ def save_depth(path, depth, as_png: bool = False, png_encoder: str = 'host') -> 
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# videos: what the reference's save_video writes (src/NerfLlffTrainerTester01.py:29-38: 15 frames a second, yuv420p), as
+# Motion-JPEG in a RIFF AVI instead of H.264 in an mp4 -- every frame a baseline JPEG whose scan is coded on the device
+# (ops.jpeg_scan, csrc/simplenerf_jpeg.h); the markers and the container are written here.
+# ITU-T T.81 Annex K.1 in zig-zag order (luminance, chrominance) and Annex K.3 as {class << 4 | id: (codes per length, symbols)}
+_JPEG_QUANT_BASE = (
+    (16, 11, 12, 14, 12, 10, 16, 14, 13, 14, 18, 17, 16, 19, 24, 40, 26, 24, 22, 22, 24, 49, 35, 37, 29, 40, 58, 51, 61, 60, 57, 51,
+     56, 55, 64, 72, 92, 78, 64, 68, 87, 69, 55, 56, 80, 109, 81, 87, 95, 98, 103, 104, 103, 62, 77, 113, 121, 112, 100, 120, 92, 101,
+     103, 99),
+    (17, 18, 18, 24, 21, 24, 47, 26, 26, 47, 99, 66, 56, 66) + (99,) * 50)
+_JPEG_HUFFMAN = {
+    0x00: (bytes([0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0]), bytes(range(12))),
+    0x10: (bytes([0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125]), bytes.fromhex(
+        '01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a4344454647'
+        '48494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9ba'
+        'c2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa')),
+    0x01: (bytes([0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0]), bytes(range(12))),
+    0x11: (bytes([0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119]), bytes.fromhex(
+        '000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a43444546'
+        '4748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8'
+        'b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa'))}
+
+
+def _jpeg_header(h: int, w: int, colour: bool, quality: int) -> bytes:
+    """Everything of a JFIF file before the entropy-coded segment ``ops.jpeg_scan`` writes: SOI, APP0 (JFIF 1.01, no density), DQT
+    (the Annex K tables scaled by ``quality`` with the libjpeg rule), SOF0 (8-bit; Y 2x2, Cb and Cr 1x1 -- or one grey component),
+    DHT (the Annex K tables), DRI (one MCU row) and SOS."""
+    import struct
+
+    def segment(marker: int, data: bytes) -> bytes:
+        return bytes([0xFF, marker]) + struct.pack('>H', len(data) + 2) + data
+
+    scale = 5000 // quality if quality < 50 else 200 - 2 * quality
+    out = b'\xff\xd8' + segment(0xE0, b'JFIF\0' + bytes([1, 1, 0, 0, 1, 0, 1, 0, 0]))
+    for table in range(2 if colour else 1):
+        out += segment(0xDB, bytes([table]) + bytes(min(255, max(1, (t * scale + 50) // 100)) for t in _JPEG_QUANT_BASE[table]))
+    components = ((1, 0x22, 0), (2, 0x11, 1), (3, 0x11, 1)) if colour else ((1, 0x11, 0),)
+    out += segment(0xC0, struct.pack('>BHHB', 8, h, w, len(components)) + b''.join(bytes(c) for c in components))
+    for key in (0x00, 0x10, 0x01, 0x11) if colour else (0x00, 0x10):
+        out += segment(0xC4, bytes([key]) + _JPEG_HUFFMAN[key][0] + _JPEG_HUFFMAN[key][1])
+    mcu = 16 if colour else 8
+    out += segment(0xDD, struct.pack('>H', (w + mcu - 1) // mcu))
+    return out + segment(0xDA, bytes([len(components)]) + b''.join(bytes([c[0], c[2] << 4 | c[2]]) for c in components) + bytes([0, 63, 0]))
+
+
+def _device_frames(value, what: str) -> Tensor:
+    if not isinstance(value, torch.Tensor) or not value.is_cuda:
+        raise RuntimeError(f"{what}: the JPEG encoder takes tensors that are on the device, got "
+                           f"{type(value).__name__}{' on ' + str(value.device) if isinstance(value, torch.Tensor) else ''}; "
+                           f"there is no host encoder to fall back to")
+    return value
+
+
+def jpeg_files(images, quality: int = 90) -> list:
+    """The JFIF files of ``images`` -- uint8 (K,h,w) grey or (K,h,w,3) RGB on the device -- as K ``bytes``, encoded there: one
+    ``ops.jpeg_scan`` call for all K (YCbCr 4:2:0, integer DCT, Annex K tables at ``quality`` 1..100, a restart interval per MCU
+    row), one copy of the K scan lengths to the host, then one copy per scan of exactly its bytes; the markers around each scan
+    (``_jpeg_header``, EOI) are written here."""
+    images = _device_frames(images, 'jpeg_files')
+    scans, sizes = ops.jpeg_scan(images, quality)
+    header = _jpeg_header(int(images.shape[1]), int(images.shape[2]), images.dim() == 4, int(quality))
+    return [header + scans[i, :n].cpu().numpy().tobytes() + b'\xff\xd9' for i, n in enumerate(sizes.cpu().tolist())]
+
+
+VIDEO_FRAME_RATE = 15          # save_video, src/NerfLlffTrainerTester01.py:34
+
+
+def _avi_bytes(frames: list, h: int, w: int, frame_rate) -> bytes:
+    """A RIFF AVI of JPEG files as one Motion-JPEG video stream: ``hdrl`` (``avih``, one ``strl`` of ``strh`` 'vids'/'MJPG' and a
+    BITMAPINFOHEADER ``strf``), ``movi`` of ``00dc`` chunks padded to even length, ``idx1`` (offsets from the 'movi' tag)."""
+    import math
+    import struct
+    from fractions import Fraction
+
+    def chunk(tag: bytes, data: bytes) -> bytes:
+        return tag + struct.pack('<I', len(data)) + data + (b'\0' if len(data) & 1 else b'')
+
+    def riff_list(kind: bytes, data: bytes) -> bytes:
+        return b'LIST' + struct.pack('<I', 4 + len(data)) + kind + data
+
+    rate = Fraction(frame_rate).limit_denominator(1000)
+    if rate <= 0:
+        raise RuntimeError(f'save_video: frame_rate {frame_rate!r} is not positive')
+    largest = max((len(f) for f in frames), default=0)
+    total = sum(len(f) for f in frames)
+    avih = struct.pack('<14I', round(1000000 / rate), math.ceil(total * rate / max(1, len(frames))), 0, 0x10, len(frames), 0, 1, largest, w, h,
+                       0, 0, 0, 0)
+    strh = struct.pack('<4s4sIHHIIIIIIIi4H', b'vids', b'MJPG', 0, 0, 0, 0, rate.denominator, rate.numerator, 0, len(frames), largest,
+                       0xFFFFFFFF, 0, 0, 0, w, h)
+    strf = struct.pack('<IiiHH4sIiiII', 40, w, h, 1, 24, b'MJPG', w * h * 3, 0, 0, 0, 0)
+    movi, index, at = [], [], 4          # (an idx1 offset counts from the 'movi' tag)
+    for data in frames:
+        index.append(struct.pack('<4sIII', b'00dc', 0x10, at, len(data)))
+        movi.append(chunk(b'00dc', data))
+        at += len(movi[-1])
+    body = (b'AVI ' + riff_list(b'hdrl', chunk(b'avih', avih) + riff_list(b'strl', chunk(b'strh', strh) + chunk(b'strf', strf)))
+            + riff_list(b'movi', b''.join(movi)) + chunk(b'idx1', b''.join(index)))
+    return b'RIFF' + struct.pack('<I', len(body)) + body
+
+
+def save_video(path, frames, frame_rate=VIDEO_FRAME_RATE, quality: int = 90) -> None:
+    """The reference's ``save_video`` (src/NerfLlffTrainerTester01.py:29-38) as Motion-JPEG: ``frames`` -- uint8 (K,h,w,3) or (K,h,w)
+    on the device -- become K baseline JPEG files there (``jpeg_files``: 4:2:0 like the reference's yuv420p) and one RIFF AVI
+    (``vids``/``MJPG``) at ``frame_rate`` frames a second on the host.  A file that exists is left alone, as the reference leaves it;
+    a file that would reach 2^31 bytes is refused (the container's index and many readers stop there)."""
+    import os
+    path = os.fspath(path)
+    if os.path.exists(path):
+        return
+    frames = _device_frames(frames, 'save_video')
+    if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or (frames.dim() == 4 and frames.shape[3] != 3):
+        raise RuntimeError(f'save_video: frames must be uint8 (K,h,w) or (K,h,w,3), got {frames.dtype} {tuple(frames.shape)}')
+    files = jpeg_files(frames, quality) if frames.shape[0] else []
+    data = _avi_bytes(files, int(frames.shape[1]), int(frames.shape[2]), frame_rate)
+    if len(data) >= 1 << 31:
+        raise RuntimeError(f'save_video: {path} would be {len(data)} bytes; an AVI of 2^31 bytes or more is not written')
+    os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+    with open(path, 'wb') as f:
+        f.write(data)
+
+
+def _select_video_frames(frames: Tensor, video_frame_nums) -> Tensor:
+    """``video_frames[video_frame_nums]`` (src/NerfLlffTrainerTester01.py:166-167): the listed frames in the listed order, repeats
+    and negative indices as numpy takes them."""
+    if video_frame_nums is None:
+        return frames
+    import numpy
+    picks = numpy.asarray(video_frame_nums).astype(int).reshape(-1)
+    count = int(frames.shape[0])
+    if picks.size and (picks.min() < -count or picks.max() >= count):
+        raise IndexError(f'video_frame_nums: index {int(picks.max() if picks.max() >= count else picks.min())} is out of bounds for {count} frames')
+    return frames[torch.from_numpy(picks % count if count else picks).to(frames.device)]
+
+
+def save_static_camera_video(model, configs: dict, preprocessor, extrinsics, out_dirpath, device, video_frame_nums=None,
+                             quality: int = 90) -> dict:
+    """The reference's StaticCameraVideo (start_testing_static_videos, src/NerfLlffTrainerTester01.py:199-228): ``extrinsics``
+    (N,4,4) raw poses; the frame of ``extrinsics[0]`` under the view cameras ``extrinsics[1:]`` (``predict_view_sweep``), the N-1
+    frames -- or those ``video_frame_nums`` lists, in its order -- written as ``StaticCameraVideo.avi`` under ``out_dirpath``
+    (``save_video``: the frames are coded where they were rendered).  The PNG frames are not written
+    (``save_static_camera_frames`` writes them).  Returns the sweep's result."""
+    import os
+    cameras = [preprocessor.camera(pose) for pose in extrinsics]
+    result = predict_view_sweep(model, configs, cameras[0], cameras[1:], device, keep_device_images=True)
+    frames = _select_video_frames(result.pop('images_device'), video_frame_nums)
+    save_video(os.path.join(os.fspath(out_dirpath), 'StaticCameraVideo.avi'), frames, quality=quality)
+    return result
+
+
+@torch.no_grad()
+def save_camera_path_video(model, configs: dict, preprocessor, extrinsics, out_dirpath, device, video_frame_nums=None,
+                           quality: int = 90) -> dict:
+    """The reference's PredictedVideo (start_testing_videos, src/NerfLlffTrainerTester01.py:141-169): each of ``extrinsics[1:]``
+    rendered as ``predict_frame`` renders it (the frame stays on the device), the N-1 frames -- or those ``video_frame_nums``
+    lists, in its order -- written as ``PredictedVideo.avi`` under ``out_dirpath``.  No PNG frames.  Returns {'images_device':
+    the (N-1,h,w,3) uint8 frames as rendered}."""
+    import os
+    ndc = bool(configs['data_loader']['ndc'])
+    suffix = '_fine' if 'fine_mlp' in configs['model'] else '_coarse'
+    keys = [f'rgb{suffix}', f'depth{suffix}', f'depth_var{suffix}'] + ([f'depth_ndc{suffix}', f'depth_var_ndc{suffix}'] if ndc else [])
+    cameras = [preprocessor.camera(pose) for pose in extrinsics]
+    h, w = (int(v) for v in cameras[0]['resolution'])
+    frames = torch.empty((max(len(cameras) - 1, 0), h, w, 3), dtype=torch.uint8, device=device)
+    for i, camera in enumerate(cameras[1:]):
+        frames[i] = display_outputs(configs, camera['resolution'], render_frame(model, camera, ndc, device, keys))['image']
+    save_video(os.path.join(os.fspath(out_dirpath), 'PredictedVideo.avi'), _select_video_frames(frames, video_frame_nums), quality=quality)
+    return {'images_device': frames}
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # the trainer's two frame loops (src/Trainer01.py: run_validation :109-263, save_sample_images :319-350)
 # per-sample outputs the reference deletes from every chunk before merging (:197-221)
 VALIDATION_DROPPED_KEYS = tuple(

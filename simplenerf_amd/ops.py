@@ -716,6 +716,36 @@ def png_deflate(images: Tensor, filter_mode: int = PNG_FILTER_ADAPTIVE):
     return streams, sizes
 
 
+JPEG_BINDINGS = ('ctypes', 'torch_ext')
+
+
+def jpeg_scan(images: Tensor, quality: int = 90, binding: str = 'ctypes'):
+    """-> (scans uint8 (K, bound), sizes int64 (K)) on the device for ``images`` uint8 (K, h, w) grey or (K, h, w, 3) RGB on the
+    device: ``scans[i, :sizes[i]]`` is the entropy-coded segment of frame i's baseline JPEG scan at ``quality`` 1..100 -- YCbCr
+    4:2:0 (or one grey component), integer DCT, the Annex K tables, one restart interval per MCU row (csrc/simplenerf_jpeg.h has the
+    contract).  The markers around a segment are the caller's (``harness.jpeg_files``).  All K frames go through one call of three
+    launches.  ``binding``: 'ctypes' (the torch-free binding) or 'torch_ext' (``torch.ops.snerf.jpeg_scan``); the same bytes."""
+    if binding not in JPEG_BINDINGS:
+        raise RuntimeError(f"binding: expected 'ctypes' or 'torch_ext', got {binding!r}")
+    images = _typed(images, 'images', (torch.uint8,))
+    if images.dim() not in (3, 4) or (images.dim() == 4 and images.shape[3] != 3):
+        raise RuntimeError(f'images: expected shape (K, h, w) or (K, h, w, 3), got {tuple(images.shape)}')
+    if binding == 'torch_ext':
+        from . import _torch_ext
+        with torch.cuda.device(images.device):
+            return tuple(_torch_ext.load().jpeg_scan(images, int(quality)))
+    count, h, w = (int(v) for v in images.shape[:3])
+    channels = 3 if images.dim() == 4 else 1
+    dev, lib = images.device, _lib.load()
+    bound = int(lib.snerf_jpeg_scan_bound_bytes(h, w, channels))
+    scans = torch.empty((count, bound), dtype=torch.uint8, device=dev)
+    sizes = torch.zeros((count,), dtype=torch.int64, device=dev)
+    workspace = _workspace('jpeg', dev, int(lib.snerf_jpeg_scan_workspace_bytes(count, h, w, channels))) if count and bound else None
+    # (an image the library does not take -- an empty one, a side above 65535 -- has bound 0 and no workspace: the call names the reason)
+    _enqueue('snerf_jpeg_scan', dev, _ptr(images), count, h, w, channels, int(quality), _ptr(scans), _ptr(sizes), _ptr(workspace))
+    return scans, sizes
+
+
 # ---------------------------------------------------------------------------------------------- Q1 frame metrics
 def _typed(t, name: str, dtypes, shape=None) -> Tensor:
     """Validate a device operand of one of ``dtypes`` (the metric inputs are uint8 / bool / float32); contiguous on return."""
