@@ -1,0 +1,110 @@
+"""The geometry a model has learnt, as something a 3-D viewer opens: the depth maps of several views fused into one coloured point
+cloud and written as a binary PLY file.
+
+A depth map alone puts a point behind every pixel, floaters included.  ``fuse_depth_maps`` keeps a pixel's point only where other
+views confirm it: the point is projected into every other view and compared with the depth that view holds at the pixel it lands on
+(nearest pixel, one-way check, relative threshold) -- the consistency filter of multi-view stereo toolkits, on the device
+(csrc/fuse.hip; csrc/simplenerf_fuse.h states the rule, tests/fuse_reference.py restates it in numpy).  ``voxel_thin`` then leaves
+one averaged point per occupied voxel.  Conventions are those of ``qa.visibility_mask`` and ``qa.forward_warp``: integer pixel
+coordinates (x = column, y = row), z-depths in the extrinsics' units, extrinsics 4x4 world-to-camera and intrinsics 3x3 (numpy or
+tensor), composed on the host in float64; fp64 device arithmetic without atomics, so the same input gives the same bits.
+
+Out of scope: meshes, normals, bilinear depth lookups, two-way reprojection checks, sharding over ranks, ASCII PLY.
+"""
+from __future__ import annotations
+
+import os
+from typing import Optional
+
+import numpy
+import torch
+
+from . import ops
+from .qa import _matrices
+
+Tensor = torch.Tensor
+PLY_VERTEX = numpy.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('red', 'u1'), ('green', 'u1'), ('blue', 'u1')])     # 15 bytes
+
+
+def fuse_cameras(extrinsics, intrinsics) -> numpy.ndarray:
+    """The (V,42) float64 table ``ops.fuse_depth_maps`` takes, inverted on the host: per view inv(K) | rows 0..2 of inv(E) | rows
+    0..2 of E | K, row-major.  ``extrinsics`` (V,4,4) world-to-camera, ``intrinsics`` (V,3,3)."""
+    views = len(extrinsics)
+    e = _matrices(extrinsics, 'extrinsics', (views, 4, 4))
+    k = _matrices(intrinsics, 'intrinsics', (views, 3, 3))
+    table = numpy.empty((views, ops.FUSE_CAMERA), dtype=numpy.float64)
+    for v in range(views):
+        table[v, 0:9] = numpy.linalg.inv(k[v]).reshape(-1)
+        table[v, 9:21] = numpy.linalg.inv(e[v])[:3].reshape(-1)
+        table[v, 21:33] = e[v, :3].reshape(-1)
+        table[v, 33:42] = k[v].reshape(-1)
+    return table
+
+
+def fuse_depth_maps(depth: Tensor, image: Tensor, extrinsics, intrinsics, depth_error_threshold: float = 0.02, min_views: int = 1,
+                    mask: Optional[Tensor] = None):
+    """-> (points float32 (N,3), colours uint8 (N,3), views uint8 (N)) on the device: the fused cloud of the float32 (V,h,w) ``depth``
+    maps and uint8 (V,h,w,3) ``image`` frames on the GPU.  A pixel is valid where its depth is finite and positive and ``mask`` (bool
+    or uint8 (V,h,w) on the GPU, optional) is set; its point P = inv(E)[:3] [d inv(K) (x, y, 1); 1] is kept when at least
+    ``min_views`` (0..V-1) of the other views agree: P lies in front of the view, projects (rounded to the nearest pixel, ties to
+    even) inside its frame onto a valid pixel of depth d_u, and |z - d_u| <= ``depth_error_threshold`` x d_u for P's depth z in that
+    view.  Points come in ascending (view, row, column) order with the pixel's colour; ``views`` is the number of agreeing views."""
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
+        raise RuntimeError(f'depth: expected a float32 tensor of shape (views, h, w) on the GPU, got '
+                           f'{tuple(depth.shape) if isinstance(depth, torch.Tensor) else type(depth).__name__}')
+    views = int(depth.shape[0])
+    cameras = fuse_cameras(_matrices(extrinsics, 'extrinsics', (views, 4, 4)), _matrices(intrinsics, 'intrinsics', (views, 3, 3)))
+    return ops.fuse_depth_maps(depth, image, torch.from_numpy(cameras).to(depth.device), depth_error_threshold, min_views, mask)
+
+
+def voxel_thin(points: Tensor, colours: Tensor, voxel_size: float):
+    """-> (points float32 (M,3), colours uint8 (M,3), counts int32 (M)) on the device: one record per voxel of side ``voxel_size``
+    (the grid starts at the per-axis minimum of ``points``) that holds a point -- the mean position, the rounded mean colour, the
+    number of points -- in ascending voxel order (z, then y, then x).  Raises when a bound of the cloud is not finite or the grid
+    would have more than 2^31 - 1 voxels."""
+    return ops.voxel_thin(points, colours, voxel_size)
+
+
+def camera_matrices(camera: dict):
+    """-> (extrinsic (4,4), intrinsic (3,3)) float64 of a camera dict as ``harness.frame_batch`` takes it.  Its ``pose`` is the
+    processed camera-to-world matrix with the camera looking down -z, y up (the ray generator flips y and z of inv(K) (x, y, 1));
+    the extrinsic here is world-to-camera with the camera looking down +z, y down, so that
+    inv(E)[:3] [t inv(K) (x, y, 1); 1] = rays_o + t rays_d and a rendered depth is the z-depth the fuse expects."""
+    pose = numpy.asarray(camera['pose'], dtype=numpy.float64).reshape(4, 4)
+    intrinsic = numpy.asarray(camera['intrinsic'], dtype=numpy.float64).reshape(3, 3)
+    camera_to_world = numpy.matmul(pose, numpy.diag([1.0, -1.0, -1.0, 1.0]))
+    return numpy.linalg.inv(camera_to_world), intrinsic.copy()
+
+
+def ply_bytes(points, colours) -> bytes:
+    """A binary little-endian PLY file of N vertices: float x, y, z and uchar red, green, blue, 15 bytes a record.  ``points`` (N,3)
+    float32 and ``colours`` (N,3) uint8, tensors (copied to the host) or numpy; N = 0 is a valid file."""
+    if isinstance(points, torch.Tensor):
+        points = points.detach().cpu().numpy()
+    if isinstance(colours, torch.Tensor):
+        colours = colours.detach().cpu().numpy()
+    points, colours = numpy.asarray(points), numpy.asarray(colours)
+    if points.dtype != numpy.float32 or points.ndim != 2 or points.shape[1] != 3:
+        raise RuntimeError(f'points: expected float32 (N, 3), got {points.dtype} {points.shape}')
+    if colours.dtype != numpy.uint8 or colours.shape != points.shape:
+        raise RuntimeError(f'colours: expected uint8 {points.shape}, got {colours.dtype} {colours.shape}')
+    records = numpy.empty((points.shape[0],), dtype=PLY_VERTEX)
+    for a, name in enumerate(('x', 'y', 'z')):
+        records[name] = points[:, a]
+    for a, name in enumerate(('red', 'green', 'blue')):
+        records[name] = colours[:, a]
+    header = ('ply\nformat binary_little_endian 1.0\n' + f'element vertex {points.shape[0]}\n'
+              + 'property float x\nproperty float y\nproperty float z\n'
+              + 'property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n')
+    return header.encode('ascii') + records.tobytes()
+
+
+def save_ply(path, points, colours) -> None:
+    """``ply_bytes`` written to ``path``.  A file that exists is left alone, as ``harness.save_video`` leaves it."""
+    path = os.fspath(path)
+    if os.path.exists(path):
+        return
+    data = ply_bytes(points, colours)
+    os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+    with open(path, 'wb') as f:
+        f.write(data)

@@ -1064,6 +1064,48 @@ def save_camera_path_video(model, configs: dict, preprocessor, extrinsics, out_d
     return {'images_device': frames}
 
 
+@torch.no_grad()
+def export_point_cloud(model, configs: dict, cameras, path, device, depth_error_threshold: float = 0.02, min_views: int = 1,
+                       voxel_size: Optional[float] = None, depth_range=None) -> dict:
+    """The model's geometry as a point cloud: every camera of ``cameras`` (dicts as ``frame_batch`` takes them, one resolution)
+    rendered as ``predict_frame`` renders it -- the 8-bit image and the depth stay on the device --, the depth maps fused
+    (``geometry.fuse_depth_maps``: a pixel's point is kept where at least ``min_views`` other views agree with it to
+    ``depth_error_threshold`` x their depth), optionally thinned to one point per voxel of ``voxel_size`` (``geometry.voxel_thin``),
+    and written to ``path`` as a binary PLY (``geometry.save_ply``: a file that exists is left alone).  ``depth_range`` = (lo, hi):
+    only pixels with lo <= depth <= hi are sources or witnesses.  The cloud is in the model's processed scene frame (recentred, and
+    scaled by ``translation_scale``); mapping it back to the data set's frame is the caller's.  Returns {'points' float32 (N,3),
+    'colours' uint8 (N,3), 'counts' (N): the agreeing views of each point (uint8), or with ``voxel_size`` the points of each voxel
+    (int32), 'fused_points': N before thinning, 'images_device' (V,h,w,3), 'depths_device' (V,h,w)}, tensors on the device."""
+    from . import geometry
+    cameras = list(cameras)
+    if not cameras:
+        raise RuntimeError('export_point_cloud: no cameras')
+    ndc = bool(configs['data_loader']['ndc'])
+    suffix = '_fine' if 'fine_mlp' in configs['model'] else '_coarse'
+    keys = [f'rgb{suffix}', f'depth{suffix}', f'depth_var{suffix}'] + ([f'depth_ndc{suffix}', f'depth_var_ndc{suffix}'] if ndc else [])
+    h, w = (int(v) for v in cameras[0]['resolution'])
+    images = torch.empty((len(cameras), h, w, 3), dtype=torch.uint8, device=device)
+    depths = torch.empty((len(cameras), h, w), dtype=torch.float32, device=device)
+    for i, camera in enumerate(cameras):
+        if tuple(int(v) for v in camera['resolution']) != (h, w):
+            raise RuntimeError(f'export_point_cloud: camera {i} has resolution {tuple(camera["resolution"])}, camera 0 has {(h, w)}')
+        shown = display_outputs(configs, camera['resolution'], render_frame(model, camera, ndc, device, keys))
+        images[i], depths[i] = shown['image'], shown['depth']
+    matrices = [geometry.camera_matrices(camera) for camera in cameras]
+    mask = None
+    if depth_range is not None:
+        low, high = (float(v) for v in depth_range)
+        mask = (depths >= low) & (depths <= high)
+    points, colours, counts = geometry.fuse_depth_maps(depths, images, [m[0] for m in matrices], [m[1] for m in matrices],
+                                                       depth_error_threshold, min_views, mask)
+    fused = int(points.shape[0])
+    if voxel_size is not None:
+        points, colours, counts = geometry.voxel_thin(points, colours, voxel_size)
+    geometry.save_ply(path, points, colours)
+    return {'points': points, 'colours': colours, 'counts': counts, 'fused_points': fused, 'images_device': images,
+            'depths_device': depths}
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # the trainer's two frame loops (src/Trainer01.py: run_validation :109-263, save_sample_images :319-350)
 # per-sample outputs the reference deletes from every chunk before merging (:197-221)

@@ -1101,6 +1101,106 @@ def warp_interpolate(frame2: Tensor, flow12: Tensor, mask2: Optional[Tensor] = N
     return warped, mask1
 
 
+# ---------------------------------------------------------------------------------------------- Q6 the point-cloud export
+FUSE_CAMERA = C.SNERF_FUSE_CAMERA_DOUBLES     # doubles per view: inv(K) 3x3 | rows 0..2 of inv(E) 3x4 | rows 0..2 of E 3x4 | K 3x3
+FUSE_MAX_VIEWS = C.SNERF_FUSE_MAX_VIEWS
+
+
+def _fuse_workspace(dev: torch.device, need: int) -> Tensor:
+    """Scratch of the two calls below (state bytes, keys, counters, the sort's buffers); 256-byte aligned like every torch allocation."""
+    return _workspace('fuse', dev, max(need, 1))
+
+
+def fuse_depth_maps(depth: Tensor, image: Tensor, cameras: Tensor, depth_error_threshold: float = 0.02, min_views: int = 1,
+                    mask: Optional[Tensor] = None):
+    """-> (points float32 (N,3), colours uint8 (N,3), views uint8 (N)) on the device: the pixels of the (V,h,w) float32 ``depth`` maps
+    (colours: the uint8 (V,h,w,3) ``image``) whose depth is finite and positive, whose ``mask`` byte (bool / uint8 (V,h,w), optional)
+    is set and whose point at least ``min_views`` of the OTHER views agree on to ``depth_error_threshold`` x their own depth at the
+    pixel it projects to, in ascending (view, row, column) order; ``views`` counts the agreeing views (csrc/simplenerf_fuse.h has the
+    rule).  ``cameras``: float64 (V,42) on the device (``geometry.fuse_cameras``).  The outputs are allocated for V h w records; N is
+    read back from the device once, to narrow them."""
+    depth = _typed(depth, 'depth', (torch.float32,))
+    if depth.dim() != 3:
+        raise RuntimeError(f'depth: expected shape (views, h, w), got {tuple(depth.shape)}')
+    views, h, w = (int(s) for s in depth.shape)
+    total = views * h * w
+    if views > FUSE_MAX_VIEWS or total > SORT_MAX_COUNT:
+        raise RuntimeError(f'depth: {views} views of {h} x {w} exceed {FUSE_MAX_VIEWS} views or the 2^31 - 1 pixels the kernels index')
+    image = _typed(image, 'image', (torch.uint8,), (views, h, w, 3))
+    cameras = _typed(cameras, 'cameras', (torch.float64,), (views, FUSE_CAMERA))
+    if mask is not None:
+        mask = _typed(mask, 'mask', (torch.bool, torch.uint8), (views, h, w))
+    if not float(depth_error_threshold) >= 0.0:
+        raise RuntimeError(f'depth_error_threshold: expected a non-negative number, got {depth_error_threshold}')
+    if isinstance(min_views, bool) or int(min_views) != min_views or not 0 <= int(min_views) <= max(views - 1, 0):
+        raise RuntimeError(f'min_views: expected 0..{max(views - 1, 0)} (the number of other views), got {min_views}')
+    dev = depth.device
+    _warp_together(dev, image=image, cameras=cameras, mask=mask)
+    points = torch.empty((total, 3), dtype=torch.float32, device=dev)
+    colours = torch.empty((total, 3), dtype=torch.uint8, device=dev)
+    agreeing = torch.empty((total,), dtype=torch.uint8, device=dev)
+    if total == 0:
+        return points, colours, agreeing
+    kept = torch.empty((1,), dtype=torch.int64, device=dev)
+    ws = _fuse_workspace(dev, int(_lib.load().snerf_fuse_depth_maps_workspace_bytes(views, h, w)))
+    _enqueue('snerf_fuse_depth_maps', dev, _ptr(depth), _ptr(image), _ptr(mask), _ptr(cameras), views, h, w, float(depth_error_threshold),
+             int(min_views), _ptr(points), _ptr(colours), _ptr(agreeing), _ptr(kept), _ptr(ws))
+    count = int(kept.item())
+    return points[:count], colours[:count], agreeing[:count]
+
+
+def voxel_grid(points: Tensor, voxel_size: float):
+    """-> (lo, extents): the per-axis minimum (three floats) of the float32 (N,3) ``points``, N >= 1, and the grid's extents in voxels,
+    n_a = floor((max_a - lo_a) / voxel_size) + 1 in float64 -- one small reduction on the device and a copy of six floats.  Raises,
+    naming ``voxel_size`` and the extents, when a bound is not finite or the grid has more than 2^31 - 1 voxels."""
+    voxel_size = float(voxel_size)
+    if not (voxel_size > 0.0 and math.isfinite(voxel_size)):
+        raise RuntimeError(f'voxel_size: expected a finite number > 0, got {voxel_size}')
+    low, high = torch.aminmax(points, dim=0)
+    bounds = torch.cat([low, high]).cpu().numpy().astype(numpy.float64)
+    if not numpy.isfinite(bounds).all():
+        raise RuntimeError(f'points: the bounds {bounds[:3].tolist()} .. {bounds[3:].tolist()} are not finite: no grid of voxel_size '
+                           f'{voxel_size} and finite extents holds them')
+    extents = tuple(int(math.floor((bounds[3 + a] - bounds[a]) / voxel_size)) + 1 for a in range(3))
+    if extents[0] * extents[1] * extents[2] > 2 ** 31 - 1:
+        raise RuntimeError(f'voxel_size: {voxel_size} gives extents {extents[0]} x {extents[1]} x {extents[2]}, more than the 2^31 - 1 '
+                           f'voxels an int32 key numbers; choose a larger voxel_size')
+    return tuple(float(v) for v in bounds[:3]), extents
+
+
+def voxel_thin(points: Tensor, colours: Tensor, voxel_size: float, lo=None, extents=None):
+    """-> (points float32 (M,3), colours uint8 (M,3), counts int32 (M)) on the device: one record per occupied voxel of the grid of
+    ``voxel_size`` with corner ``lo`` and ``extents`` voxels (both from ``voxel_grid`` when not given), in ascending voxel order (z,
+    then y, then x): the mean position (a sequential float64 sum in source order), the rounded mean colour and the number of the
+    float32 (N,3) ``points`` / uint8 (N,3) ``colours`` in it (csrc/simplenerf_fuse.h has the rule).  M is read back once."""
+    points = _typed(points, 'points', (torch.float32,))
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError(f'points: expected shape (N, 3), got {tuple(points.shape)}')
+    n = int(points.shape[0])
+    if n > SORT_MAX_COUNT:
+        raise RuntimeError(f'points: {n} points exceed the 2^31 - 1 the sort kernels index')
+    colours = _typed(colours, 'colours', (torch.uint8,), (n, 3))
+    dev = points.device
+    _warp_together(dev, colours=colours)
+    thinned, thinned_colours = torch.empty_like(points), torch.empty_like(colours)
+    counts = torch.empty((n,), dtype=torch.int32, device=dev)
+    if n == 0:
+        if not (float(voxel_size) > 0.0 and math.isfinite(float(voxel_size))):
+            raise RuntimeError(f'voxel_size: expected a finite number > 0, got {voxel_size}')
+        return thinned, thinned_colours, counts
+    if lo is None or extents is None:
+        lo, extents = voxel_grid(points, voxel_size)
+    lo, extents = tuple(float(v) for v in lo), tuple(int(v) for v in extents)
+    if len(lo) != 3 or len(extents) != 3:
+        raise RuntimeError(f'lo, extents: expected three values each, got {lo} and {extents}')
+    runs = torch.empty((1,), dtype=torch.int64, device=dev)
+    ws = _fuse_workspace(dev, int(_lib.load().snerf_voxel_thin_workspace_bytes(n, *extents)))
+    _enqueue('snerf_voxel_thin', dev, _ptr(points), _ptr(colours), n, float(voxel_size), *lo, *extents, _ptr(thinned),
+             _ptr(thinned_colours), _ptr(counts), _ptr(runs), _ptr(ws))
+    count = int(runs.item())
+    return thinned[:count], thinned_colours[:count], counts[:count]
+
+
 # ---------------------------------------------------------------------------------------------- f1 losses
 class LossTermSpec:
     """One masked mean-squared-error term of the fused loss evaluation (struct snerf_loss_term).  ``two_sided``: the
