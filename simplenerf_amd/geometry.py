@@ -1,5 +1,5 @@
 """The geometry a model has learnt, as something a 3-D viewer opens: the depth maps of several views fused into one coloured point
-cloud and written as a binary PLY file.
+cloud, or into a triangle mesh, and written as a binary PLY file.
 
 A depth map alone puts a point behind every pixel, floaters included.  ``fuse_depth_maps`` keeps a pixel's point only where other
 views confirm it: the point is projected into every other view and compared with the depth that view holds at the pixel it lands on
@@ -9,7 +9,14 @@ one averaged point per occupied voxel.  Conventions are those of ``qa.visibility
 coordinates (x = column, y = row), z-depths in the extrinsics' units, extrinsics 4x4 world-to-camera and intrinsics 3x3 (numpy or
 tensor), composed on the host in float64; fp64 device arithmetic without atomics, so the same input gives the same bits.
 
-Out of scope: meshes, normals, bilinear depth lookups, two-way reprojection checks, sharding over ranks, ASCII PLY.
+A surface comes from the same depth maps in three steps (csrc/mesh.hip; csrc/simplenerf_mesh.h states the rules, tests/mesh_reference.py
+restates them): ``tsdf_volume`` averages truncated signed distances into a regular grid, ``extract_mesh`` runs marching tetrahedra
+over it (six Kuhn tetrahedra a cell: no ambiguous case, watertight wherever the volume is observed), ``colour_points`` colours the
+vertices from the frames; ``save_ply_mesh`` writes the indexed file.
+
+Out of scope: marching cubes, Poisson reconstruction, normals, bilinear depth lookups, view-angle or distance
+weighting, sparse or hashed volumes, dropping zero-area triangles, welding coincident vertices, two-way reprojection checks, sharding
+over ranks, ASCII PLY, meshing the density field directly.
 """
 from __future__ import annotations
 
@@ -23,6 +30,7 @@ from . import ops
 from .qa import _matrices
 
 Tensor = torch.Tensor
+PLY_FACE = numpy.dtype([('count', 'u1'), ('a', '<i4'), ('b', '<i4'), ('c', '<i4')])     # 13 bytes
 PLY_VERTEX = numpy.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('red', 'u1'), ('green', 'u1'), ('blue', 'u1')])     # 15 bytes
 
 
@@ -105,6 +113,71 @@ def save_ply(path, points, colours) -> None:
     if os.path.exists(path):
         return
     data = ply_bytes(points, colours)
+    os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+    with open(path, 'wb') as f:
+        f.write(data)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the mesh
+def _views_of(depth, extrinsics, intrinsics):
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
+        raise RuntimeError(f'depth: expected a float32 tensor of shape (views, h, w) on the GPU, got '
+                           f'{tuple(depth.shape) if isinstance(depth, torch.Tensor) else type(depth).__name__}')
+    views = int(depth.shape[0])
+    cameras = fuse_cameras(_matrices(extrinsics, 'extrinsics', (views, 4, 4)), _matrices(intrinsics, 'intrinsics', (views, 3, 3)))
+    return torch.from_numpy(cameras.reshape(views, ops.FUSE_CAMERA)).to(depth.device)
+
+
+def tsdf_volume(depth: Tensor, extrinsics, intrinsics, lo, voxel_size: float, extents, truncation: float, mask: Optional[Tensor] = None):
+    """-> (tsdf float32 (nz,ny,nx), weight uint8 (nz,ny,nx)) on the device: the float32 (V,h,w) ``depth`` maps on the GPU fused into
+    the grid of ``extents`` = (nx,ny,nz) nodes whose node (i,j,k) sits at ``lo`` + ``voxel_size`` (i,j,k).  A view contributes to a
+    node that lies in front of it and projects (nearest pixel, ties to even) inside its frame onto a valid pixel (finite positive
+    depth d, ``mask`` set) no more than ``truncation`` in front of the node: min(1, (d - z) / truncation) for the node's depth z in
+    that view.  ``tsdf`` is the mean over the contributing views (1 where there is none), ``weight`` their number."""
+    return ops.tsdf_integrate(depth, _views_of(depth, extrinsics, intrinsics), lo, voxel_size, extents, truncation, mask)
+
+
+def extract_mesh(tsdf: Tensor, weight: Tensor, lo, voxel_size: float, min_weight: int = 1):
+    """-> (vertices float32 (Nv,3), triangles int32 (Nt,3)) on the device: the surface tsdf = 0 by marching tetrahedra over the cells
+    of the volume whose eight nodes all have ``weight`` >= ``min_weight``.  A vertex lies on a grid edge whose nodes differ in sign
+    (a node is negative where tsdf < 0), interpolated linearly; triangles are wound so that their normals look from the negative side
+    to the positive one, i.e. out of the surface and towards the cameras.  Zero-area triangles (a surface through a node) are kept."""
+    return ops.mesh_extract(tsdf, weight, lo, voxel_size, min_weight)
+
+
+def colour_points(points: Tensor, depth: Tensor, image: Tensor, extrinsics, intrinsics, colour_tolerance: float,
+                  mask: Optional[Tensor] = None):
+    """-> (colours uint8 (N,3), views uint8 (N)) on the device: every float32 (N,3) point coloured with the rounded mean of the
+    uint8 (V,h,w,3) ``image`` pixels it projects to in the views whose valid depth there is within ``colour_tolerance`` (scene units)
+    of the point's own depth in that view; ``views`` counts them, and the colour is (0,0,0) where it is 0."""
+    return ops.colour_points(points, depth, image, _views_of(depth, extrinsics, intrinsics), colour_tolerance, mask)
+
+
+def ply_mesh_bytes(points, colours, triangles) -> bytes:
+    """A binary little-endian PLY file of N vertices as ``ply_bytes`` writes them and F faces: ``property list uchar int
+    vertex_indices``, 13 bytes a face.  ``triangles`` (F,3) int32, a tensor (copied to the host) or numpy; F = 0 and N = 0 are valid."""
+    if isinstance(triangles, torch.Tensor):
+        triangles = triangles.detach().cpu().numpy()
+    triangles = numpy.asarray(triangles)
+    if triangles.dtype != numpy.int32 or triangles.ndim != 2 or triangles.shape[1] != 3:
+        raise RuntimeError(f'triangles: expected int32 (F, 3), got {triangles.dtype} {triangles.shape}')
+    vertex_file = ply_bytes(points, colours)
+    end = b'end_header\n'
+    header, records = vertex_file.split(end, 1)
+    faces = numpy.empty((triangles.shape[0],), dtype=PLY_FACE)
+    faces['count'] = 3
+    for a, name in enumerate(('a', 'b', 'c')):
+        faces[name] = triangles[:, a]
+    return (header + f'element face {triangles.shape[0]}\nproperty list uchar int vertex_indices\n'.encode('ascii') + end + records
+            + faces.tobytes())
+
+
+def save_ply_mesh(path, points, colours, triangles) -> None:
+    """``ply_mesh_bytes`` written to ``path``.  A file that exists is left alone, as ``save_ply`` leaves it."""
+    path = os.fspath(path)
+    if os.path.exists(path):
+        return
+    data = ply_mesh_bytes(points, colours, triangles)
     os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
     with open(path, 'wb') as f:
         f.write(data)

@@ -9,8 +9,10 @@ frame loops, Trainer.run_validation (src/Trainer01.py:109-263) and save_sample_i
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Dict, Iterable, Optional, Tuple
 
+import numpy
 import torch
 
 from . import _lib, ops
@@ -1065,6 +1067,35 @@ def save_camera_path_video(model, configs: dict, preprocessor, extrinsics, out_d
 
 
 @torch.no_grad()
+def _render_views(what: str, model, configs: dict, cameras, device, depth_range):
+    """The renders the geometry exports share: every camera of ``cameras`` (dicts as ``frame_batch`` takes them, one resolution)
+    rendered as ``predict_frame`` renders it, the 8-bit images and the depths staying on the device.  -> (images uint8 (V,h,w,3),
+    depths float32 (V,h,w), extrinsics, intrinsics (lists of float64 matrices, ``geometry.camera_matrices``), mask: the pixels with
+    lo <= depth <= hi of ``depth_range`` = (lo, hi), or None).  Refusals are reported under ``what``."""
+    from . import geometry
+    cameras = list(cameras)
+    if not cameras:
+        raise RuntimeError(f'{what}: no cameras')
+    ndc = bool(configs['data_loader']['ndc'])
+    suffix = '_fine' if 'fine_mlp' in configs['model'] else '_coarse'
+    keys = [f'rgb{suffix}', f'depth{suffix}', f'depth_var{suffix}'] + ([f'depth_ndc{suffix}', f'depth_var_ndc{suffix}'] if ndc else [])
+    h, w = (int(v) for v in cameras[0]['resolution'])
+    images = torch.empty((len(cameras), h, w, 3), dtype=torch.uint8, device=device)
+    depths = torch.empty((len(cameras), h, w), dtype=torch.float32, device=device)
+    for i, camera in enumerate(cameras):
+        if tuple(int(v) for v in camera['resolution']) != (h, w):
+            raise RuntimeError(f'{what}: camera {i} has resolution {tuple(camera["resolution"])}, camera 0 has {(h, w)}')
+        shown = display_outputs(configs, camera['resolution'], render_frame(model, camera, ndc, device, keys))
+        images[i], depths[i] = shown['image'], shown['depth']
+    matrices = [geometry.camera_matrices(camera) for camera in cameras]
+    mask = None
+    if depth_range is not None:
+        low, high = (float(v) for v in depth_range)
+        mask = (depths >= low) & (depths <= high)
+    return images, depths, [m[0] for m in matrices], [m[1] for m in matrices], mask
+
+
+@torch.no_grad()
 def export_point_cloud(model, configs: dict, cameras, path, device, depth_error_threshold: float = 0.02, min_views: int = 1,
                        voxel_size: Optional[float] = None, depth_range=None) -> dict:
     """The model's geometry as a point cloud: every camera of ``cameras`` (dicts as ``frame_batch`` takes them, one resolution)
@@ -1077,33 +1108,55 @@ def export_point_cloud(model, configs: dict, cameras, path, device, depth_error_
     'colours' uint8 (N,3), 'counts' (N): the agreeing views of each point (uint8), or with ``voxel_size`` the points of each voxel
     (int32), 'fused_points': N before thinning, 'images_device' (V,h,w,3), 'depths_device' (V,h,w)}, tensors on the device."""
     from . import geometry
-    cameras = list(cameras)
-    if not cameras:
-        raise RuntimeError('export_point_cloud: no cameras')
-    ndc = bool(configs['data_loader']['ndc'])
-    suffix = '_fine' if 'fine_mlp' in configs['model'] else '_coarse'
-    keys = [f'rgb{suffix}', f'depth{suffix}', f'depth_var{suffix}'] + ([f'depth_ndc{suffix}', f'depth_var_ndc{suffix}'] if ndc else [])
-    h, w = (int(v) for v in cameras[0]['resolution'])
-    images = torch.empty((len(cameras), h, w, 3), dtype=torch.uint8, device=device)
-    depths = torch.empty((len(cameras), h, w), dtype=torch.float32, device=device)
-    for i, camera in enumerate(cameras):
-        if tuple(int(v) for v in camera['resolution']) != (h, w):
-            raise RuntimeError(f'export_point_cloud: camera {i} has resolution {tuple(camera["resolution"])}, camera 0 has {(h, w)}')
-        shown = display_outputs(configs, camera['resolution'], render_frame(model, camera, ndc, device, keys))
-        images[i], depths[i] = shown['image'], shown['depth']
-    matrices = [geometry.camera_matrices(camera) for camera in cameras]
-    mask = None
-    if depth_range is not None:
-        low, high = (float(v) for v in depth_range)
-        mask = (depths >= low) & (depths <= high)
-    points, colours, counts = geometry.fuse_depth_maps(depths, images, [m[0] for m in matrices], [m[1] for m in matrices],
-                                                       depth_error_threshold, min_views, mask)
+    images, depths, extrinsics, intrinsics, mask = _render_views('export_point_cloud', model, configs, cameras, device, depth_range)
+    points, colours, counts = geometry.fuse_depth_maps(depths, images, extrinsics, intrinsics, depth_error_threshold, min_views, mask)
     fused = int(points.shape[0])
     if voxel_size is not None:
         points, colours, counts = geometry.voxel_thin(points, colours, voxel_size)
     geometry.save_ply(path, points, colours)
     return {'points': points, 'colours': colours, 'counts': counts, 'fused_points': fused, 'images_device': images,
             'depths_device': depths}
+
+
+@torch.no_grad()
+def export_mesh(model, configs: dict, cameras, path, device, voxel_size: float, truncation: Optional[float] = None, bounds=None,
+                min_weight: int = 1, colour_tolerance: Optional[float] = None, depth_range=None) -> dict:
+    """The model's geometry as a triangle mesh: every camera of ``cameras`` rendered as ``export_point_cloud`` renders it, the depth
+    maps fused into a truncated signed distance volume of ``voxel_size`` (``geometry.tsdf_volume``; ``truncation`` defaults to four
+    voxels), the surface extracted by marching tetrahedra over the cells that at least ``min_weight`` views observed at every corner
+    (``geometry.extract_mesh``), its vertices coloured from the frames (``geometry.colour_points``; ``colour_tolerance`` defaults
+    to one voxel) and written to ``path`` as a binary PLY (``geometry.save_ply_mesh``: a file that exists is left alone).
+    ``bounds`` = ((x0, y0, z0), (x1, y1, z1)) is the box the grid covers; it defaults to the box of all valid pixels' points, padded
+    by the truncation.  ``depth_range`` = (lo, hi): only pixels with lo <= depth <= hi are used.  Raises, naming the limit
+    7 nx ny nz <= 2^31 - 1, when the grid is too large.  The mesh is in the model's processed scene frame.  Returns {'vertices'
+    float32 (Nv,3), 'colours' uint8 (Nv,3), 'views' uint8 (Nv), 'triangles' int32 (Nt,3), 'tsdf' float32 (nz,ny,nx), 'weight' uint8
+    (nz,ny,nx), 'lo', 'voxel_size', 'extents' (nx,ny,nz), 'truncation', 'images_device', 'depths_device'}, tensors on the device."""
+    from . import geometry
+    voxel_size = float(voxel_size)
+    if not (voxel_size > 0.0 and math.isfinite(voxel_size)):
+        raise RuntimeError(f'export_mesh: voxel_size: expected a finite number > 0, got {voxel_size}')
+    truncation = 4.0 * voxel_size if truncation is None else float(truncation)
+    colour_tolerance = voxel_size if colour_tolerance is None else float(colour_tolerance)
+    images, depths, extrinsics, intrinsics, mask = _render_views('export_mesh', model, configs, cameras, device, depth_range)
+    if bounds is None:
+        points = geometry.fuse_depth_maps(depths, images, extrinsics, intrinsics, 0.0, 0, mask)[0]
+        if points.shape[0] == 0:
+            raise RuntimeError('export_mesh: no pixel has a valid depth, so there are no bounds to cover; pass bounds')
+        low, high = torch.aminmax(points, dim=0)
+        box = torch.cat([low, high]).cpu().numpy().astype(numpy.float64)
+        low, high = box[:3] - truncation, box[3:] + truncation
+    else:
+        low, high = (numpy.asarray(b, dtype=numpy.float64).reshape(3) for b in bounds)
+    if not (numpy.isfinite(low).all() and numpy.isfinite(high).all() and (high >= low).all()):
+        raise RuntimeError(f'export_mesh: bounds {low.tolist()} .. {high.tolist()} are not a finite box')
+    extents = tuple(int(math.floor((high[a] - low[a]) / voxel_size)) + 2 for a in range(3))     # (the last node at or past the bound)
+    lo, voxel_size, extents = ops.mesh_grid(low.tolist(), voxel_size, extents)
+    tsdf, weight = geometry.tsdf_volume(depths, extrinsics, intrinsics, lo, voxel_size, extents, truncation, mask)
+    vertices, triangles = geometry.extract_mesh(tsdf, weight, lo, voxel_size, min_weight)
+    colours, views = geometry.colour_points(vertices, depths, images, extrinsics, intrinsics, colour_tolerance, mask)
+    geometry.save_ply_mesh(path, vertices, colours, triangles)
+    return {'vertices': vertices, 'colours': colours, 'views': views, 'triangles': triangles, 'tsdf': tsdf, 'weight': weight, 'lo': lo,
+            'voxel_size': voxel_size, 'extents': extents, 'truncation': truncation, 'images_device': images, 'depths_device': depths}
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -1201,6 +1201,117 @@ def voxel_thin(points: Tensor, colours: Tensor, voxel_size: float, lo=None, exte
     return thinned[:count], thinned_colours[:count], counts[:count]
 
 
+# ---------------------------------------------------------------------------------------------- Q7 the mesh export
+MESH_KEYS_PER_NODE = C.SNERF_MESH_KEYS_PER_NODE     # a grid may have 7 nx ny nz <= 2^31 - 1
+
+
+def mesh_grid(lo, voxel_size, extents):
+    """-> (lo (three floats), voxel_size, extents (nx, ny, nz)) of a volume, checked: ``voxel_size`` and ``lo`` finite, ``voxel_size``
+    > 0, extents >= 1 and 7 nx ny nz <= 2^31 - 1 (csrc/simplenerf_mesh.h); refused by name otherwise."""
+    voxel_size = float(voxel_size)
+    if not (voxel_size > 0.0 and math.isfinite(voxel_size)):
+        raise RuntimeError(f'voxel_size: expected a finite number > 0, got {voxel_size}')
+    lo = tuple(float(v) for v in lo)
+    if len(lo) != 3 or not all(math.isfinite(v) for v in lo):
+        raise RuntimeError(f'lo: expected three finite numbers, got {lo}')
+    extents = tuple(extents)
+    if len(extents) != 3 or any(isinstance(n, bool) or int(n) != n or int(n) < 1 for n in extents):
+        raise RuntimeError(f'extents: expected three integers >= 1 (nx, ny, nz), got {extents}')
+    extents = tuple(int(n) for n in extents)
+    if MESH_KEYS_PER_NODE * extents[0] * extents[1] * extents[2] > SORT_MAX_COUNT:
+        raise RuntimeError(f'extents: {extents[0]} x {extents[1]} x {extents[2]} nodes exceed the limit 7 nx ny nz <= 2^31 - 1 of the '
+                           f'mesh kernels; choose a larger voxel_size or smaller bounds')
+    return lo, voxel_size, extents
+
+
+def _mesh_views(depth, cameras, mask, image=None):
+    """The (V,h,w) float32 depth maps of a mesh call with their camera table, mask and frames, checked as ``fuse_depth_maps`` checks."""
+    depth = _typed(depth, 'depth', (torch.float32,))
+    if depth.dim() != 3:
+        raise RuntimeError(f'depth: expected shape (views, h, w), got {tuple(depth.shape)}')
+    views, h, w = (int(s) for s in depth.shape)
+    if views > FUSE_MAX_VIEWS or views * h * w > SORT_MAX_COUNT:
+        raise RuntimeError(f'depth: {views} views of {h} x {w} exceed {FUSE_MAX_VIEWS} views or the 2^31 - 1 pixels the kernels index')
+    cameras = _typed(cameras, 'cameras', (torch.float64,), (views, FUSE_CAMERA))
+    if mask is not None:
+        mask = _typed(mask, 'mask', (torch.bool, torch.uint8), (views, h, w))
+    if image is not None:
+        image = _typed(image, 'image', (torch.uint8,), (views, h, w, 3))
+    _warp_together(depth.device, cameras=cameras, mask=mask, image=image)
+    return depth, cameras, mask, image, views, h, w
+
+
+def tsdf_integrate(depth: Tensor, cameras: Tensor, lo, voxel_size: float, extents, truncation: float, mask: Optional[Tensor] = None):
+    """-> (tsdf float32 (nz,ny,nx), weight uint8 (nz,ny,nx)) on the device: per node of the grid (node (i,j,k) at ``lo`` +
+    ``voxel_size`` (i,j,k), ``extents`` = (nx,ny,nz)) the mean over the views that see it of min(1, (d - z) / ``truncation``), d the
+    valid depth of the pixel the node projects to and z the node's depth in the view, where d - z >= -``truncation``; ``weight``
+    counts those views, and tsdf is 1 where it is 0 (csrc/simplenerf_mesh.h has the rule).  ``depth`` float32 (V,h,w), ``cameras``
+    float64 (V,42) (``geometry.fuse_cameras``), ``mask`` bool / uint8 (V,h,w), optional."""
+    depth, cameras, mask, _, views, h, w = _mesh_views(depth, cameras, mask)
+    lo, voxel_size, extents = mesh_grid(lo, voxel_size, extents)
+    truncation = float(truncation)
+    if not (truncation > 0.0 and math.isfinite(truncation)):
+        raise RuntimeError(f'truncation: expected a finite number > 0, got {truncation}')
+    dev = depth.device
+    nx, ny, nz = extents
+    tsdf = torch.empty((nz, ny, nx), dtype=torch.float32, device=dev)
+    weight = torch.empty((nz, ny, nx), dtype=torch.uint8, device=dev)
+    _enqueue('snerf_tsdf_integrate', dev, _ptr(depth), _ptr(mask), _ptr(cameras), views, h, w, voxel_size, *lo, nx, ny, nz, truncation,
+             _ptr(tsdf), _ptr(weight))
+    return tsdf, weight
+
+
+def mesh_extract(tsdf: Tensor, weight: Tensor, lo, voxel_size: float, min_weight: int = 1):
+    """-> (vertices float32 (Nv,3), triangles int32 (Nt,3)) on the device: the marching-tetrahedra surface tsdf = 0 of a float32
+    (nz,ny,nx) ``tsdf`` volume over the cells whose eight nodes all have uint8 ``weight`` >= ``min_weight`` (1..255); vertices in
+    ascending (node, edge type) order, triangles in ascending (cell, tetrahedron) order (csrc/simplenerf_mesh.h has the rule).
+    Count, read the two counts back (the one synchronisation), allocate, emit."""
+    tsdf = _typed(tsdf, 'tsdf', (torch.float32,))
+    if tsdf.dim() != 3 or 0 in tsdf.shape:
+        raise RuntimeError(f'tsdf: expected shape (nz, ny, nx), every extent >= 1, got {tuple(tsdf.shape)}')
+    nz, ny, nx = (int(s) for s in tsdf.shape)
+    weight = _typed(weight, 'weight', (torch.uint8,), (nz, ny, nx))
+    lo, voxel_size, extents = mesh_grid(lo, voxel_size, (nx, ny, nz))
+    if isinstance(min_weight, bool) or int(min_weight) != min_weight or not 1 <= int(min_weight) <= 255:
+        raise RuntimeError(f'min_weight: expected 1..255, got {min_weight}')
+    dev = tsdf.device
+    _warp_together(dev, weight=weight)
+    counts = torch.empty((2,), dtype=torch.int64, device=dev)
+    ws = _workspace('mesh', dev, max(int(_lib.load().snerf_mesh_workspace_bytes(nx, ny, nz)), 1))
+    grid = (_ptr(tsdf), _ptr(weight), voxel_size, *lo, nx, ny, nz, int(min_weight), _ptr(counts))
+    _enqueue('snerf_mesh_count', dev, *grid, _ptr(ws))
+    num_vertices, num_triangles = (int(v) for v in counts.tolist())
+    vertices = torch.empty((num_vertices, 3), dtype=torch.float32, device=dev)
+    triangles = torch.empty((num_triangles, 3), dtype=torch.int32, device=dev)
+    if num_vertices > 0 and num_triangles > 0:
+        _enqueue('snerf_mesh_emit', dev, *grid, _ptr(vertices), _ptr(triangles), _ptr(ws))
+    return vertices, triangles
+
+
+def colour_points(points: Tensor, depth: Tensor, image: Tensor, cameras: Tensor, colour_tolerance: float, mask: Optional[Tensor] = None):
+    """-> (colours uint8 (N,3), views uint8 (N)) on the device: per float32 (N,3) point the rounded mean of the pixels it projects to
+    in the views that agree with it -- the pixel is valid and its depth within ``colour_tolerance`` (scene units) of the point's depth
+    in that view -- and the number of those views; (0,0,0) where none agrees (csrc/simplenerf_mesh.h has the rule).  ``depth``,
+    ``image``, ``cameras``, ``mask`` as ``fuse_depth_maps`` takes them."""
+    points = _typed(points, 'points', (torch.float32,))
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError(f'points: expected shape (N, 3), got {tuple(points.shape)}')
+    n = int(points.shape[0])
+    if n > SORT_MAX_COUNT:
+        raise RuntimeError(f'points: {n} points exceed the 2^31 - 1 the kernels index')
+    depth, cameras, mask, image, views, h, w = _mesh_views(depth, cameras, mask, _typed(image, 'image', (torch.uint8,)))
+    if not float(colour_tolerance) >= 0.0:
+        raise RuntimeError(f'colour_tolerance: expected a non-negative number, got {colour_tolerance}')
+    dev = points.device
+    _warp_together(dev, depth=depth)
+    colours = torch.empty((n, 3), dtype=torch.uint8, device=dev)
+    agreeing = torch.empty((n,), dtype=torch.uint8, device=dev)
+    if n > 0:
+        _enqueue('snerf_colour_points', dev, _ptr(points), n, _ptr(depth), _ptr(image), _ptr(mask), _ptr(cameras), views, h, w,
+                 float(colour_tolerance), _ptr(colours), _ptr(agreeing))
+    return colours, agreeing
+
+
 # ---------------------------------------------------------------------------------------------- f1 losses
 class LossTermSpec:
     """One masked mean-squared-error term of the fused loss evaluation (struct snerf_loss_term).  ``two_sided``: the
