@@ -308,21 +308,30 @@ def pe_feature(n, h, pairs, degree):
     return {0: 0, 1: 2, 2: 1}.get((n - pairs) * 2 + h, -1)
 
 
-def decode_fused(saved, cfg, total, bf16):
+def decode_fused(saved, cfg, total, bf16, blocks=None):
     """forward_train's saved tensor of the fused 16-bit modes -> natural-order float64 activations and bool masks per sample.
     Per 32-sample wave block, act16_rows rows of 32 x 16 bit: pe (4 pieces) | pev (2) | h_1 .. h_D | feature | h_v | mask words.
     A 1-KiB piece is one 16-feature k-step, [slot = 2 sample + lane half][8 elements]: element e of half h is feature
     16 p + 8 (e >> 2) + 4 h + (e & 3) of an activation, PE register 8 p + e of an encoding.  Mask word pair t >> 1, lane
-    sample + 32 half, bit 16 (t & 1) + r <-> feature 32 u + (r & 3) + 8 (r >> 2) + 4 half of tile t (test_gpu_grads.py:136-154)."""
+    sample + 32 half, bit 16 (t & 1) + r <-> feature 32 u + (r & 3) + 8 (r >> 2) + 4 half of tile t (test_gpu_grads.py:136-154).
+    `blocks`: wave-block indices to decode (gathered on the device, so only they move to the host); the rows are then the real
+    samples of those blocks in order, their indices in dec['samples']."""
     p = plan_of(cfg)
     D, W, vw = p['depth'], p['width'], p['views_width']
     act_mask = 96 + (D + 1) * W + vw
     tiles = D * (W // 32) + vw // 32
     rows = act_mask + 4 * ((tiles + 1) // 2)
-    halfs = saved.cpu().view(torch.int16)            # (sized for the fp32 layout's longer blocks: the 16-bit blocks use its front)
-    blocks = -(-total // 32)
-    assert blocks * rows * 32 <= halfs.numel(), (halfs.numel(), rows, total)
-    blk = halfs[:blocks * rows * 32].reshape(blocks, rows * 32)
+    halfs = saved.view(torch.int16)                  # (sized for the fp32 layout's longer blocks: the 16-bit blocks use its front)
+    all_blocks = -(-total // 32)
+    assert all_blocks * rows * 32 <= halfs.numel(), (halfs.numel(), rows, total)
+    blk = halfs[:all_blocks * rows * 32].reshape(all_blocks, rows * 32)
+    index = torch.arange(all_blocks) if blocks is None else torch.as_tensor(list(blocks), dtype=torch.int64)
+    assert index.numel() == 0 or (0 <= int(index.min()) and int(index.max()) < all_blocks), (blocks, all_blocks)
+    blk = (blk if blocks is None else blk[index.to(blk.device)]).cpu()
+    blocks = index.numel()
+    samples = (index[:, None] * 32 + torch.arange(32)).reshape(-1)
+    live = samples < total                           # (all but the tail of the call's last block)
+    samples, total = samples[live], int(live.sum())
 
     def value(bits):
         if bf16:
@@ -331,11 +340,11 @@ def decode_fused(saved, cfg, total, bf16):
 
     def region(r0, nfeat):
         x = blk[:, r0 * 32:(r0 + nfeat) * 32].reshape(blocks, nfeat // 16, 32, 2, 2, 4)      # piece, sample, h, g, q
-        return value(x.permute(0, 2, 1, 4, 3, 5).reshape(blocks * 32, nfeat)[:total].contiguous())
+        return value(x.permute(0, 2, 1, 4, 3, 5).reshape(blocks * 32, nfeat)[live].contiguous())
 
     def encoding(r0, npieces, pairs, degree, nfeat):
         raw = value(blk[:, r0 * 32:r0 * 32 + npieces * 512].reshape(blocks, npieces, 32, 2, 8).permute(0, 2, 1, 3, 4)
-                    .reshape(blocks * 32, npieces * 16)[:total].contiguous())            # column 16 p + 8 h + e
+                    .reshape(blocks * 32, npieces * 16)[live].contiguous())              # column 16 p + 8 h + e
         out = torch.zeros(total, nfeat, dtype=torch.float64)
         for q in range(npieces):
             for h in range(2):
@@ -355,10 +364,10 @@ def decode_fused(saved, cfg, total, bf16):
             for h in range(2):
                 for r in range(16):
                     out[:, :, 32 * u + (r & 3) + 8 * (r >> 2) + 4 * h] = ((words[:, t >> 1, h, :] >> (16 * (t & 1) + r)) & 1).bool()
-        return out.reshape(blocks * 32, ntiles * 32)[:total]
+        return out.reshape(blocks * 32, ntiles * 32)[live]
 
     pe_full = p['pe_full']
-    dec = {'pe': encoding(0, 4, 30, cfg['points_positional_encoding_degree'], pe_full),
+    dec = {'samples': samples, 'pe': encoding(0, 4, 30, cfg['points_positional_encoding_degree'], pe_full),
            'h': [region(96 + l * W, W) for l in range(D)], 'mask': [masks(l * (W // 32), W // 32) for l in range(D)]}
     if p['view_dep']:
         dec['pev'] = encoding(64, 2, 12, cfg['views_positional_encoding_degree'], p['views_pe'])
