@@ -22,6 +22,7 @@
 
 #include "snerf_common.h"
 #include "simplenerf_mesh.h"
+#include "mesh_lookup.h"
 #include "mesh_tables.h"
 #include "sort_plan.h"
 #include "tile_scan.h"
@@ -32,9 +33,6 @@ using namespace snerf::sortplan;
 using namespace snerf::tilescan;
 using namespace snerf::mesh;
 
-constexpr int kCamera = SNERF_FUSE_CAMERA_DOUBLES;
-constexpr int kE = 21, kK = 33;                                // offsets of E[:3] and K in a view's row of the camera table
-static_assert(kK + 9 == kCamera, "the camera row is inv(K) | inv(E)[:3] | E[:3] | K");
 static_assert(kKeysPerNode == SNERF_MESH_KEYS_PER_NODE, "mesh_tables.h and simplenerf_mesh.h number the same keys");
 constexpr unsigned char kComplete = 0x80;                      // cell byte: kComplete | triangles (0 .. 12)
 
@@ -46,39 +44,16 @@ struct Views {
     long long pixels;               // height * width
 };
 
-struct Grid {
-    double voxel_size, lo[3];
-    int n[3];
-    long long nodes;                // nx ny nz; 7 nodes <= 2^31 - 1
-};
-
 // The lookup of P in view u: false when the view does not see P or the pixel it lands on is not valid; else *c_z is P's depth in
 // the view and *pixel the index of that pixel in (views, height, width).
 __device__ __forceinline__ bool look_up(const Views& f, const double P[3], int u, double* c_z, long long* pixel) {
-    const double* E = f.cameras + (long long)u * kCamera + kE;
-    const double* K = f.cameras + (long long)u * kCamera + kK;
-    double c[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) c[a] = ((E[4 * a] * P[0] + E[4 * a + 1] * P[1]) + E[4 * a + 2] * P[2]) + E[4 * a + 3];
-    if (!(c[2] > 0.0)) return false;
-    const double q0 = (K[0] * c[0] + K[1] * c[1]) + K[2] * c[2];
-    const double q1 = (K[3] * c[0] + K[4] * c[1]) + K[5] * c[2];
-    const double q2 = (K[6] * c[0] + K[7] * c[1]) + K[8] * c[2];
-    const double ix = rint(q0 / q2), iy = rint(q1 / q2);
-    if (!(ix >= 0.0 && ix < (double)f.width && iy >= 0.0 && iy < (double)f.height)) return false;     // (a NaN fails every comparison)
+    double ix, iy;
+    if (!view_pixel(f.cameras, u, f.height, f.width, P, c_z, &ix, &iy)) return false;
     const long long j = (long long)u * f.pixels + (long long)iy * f.width + (long long)ix;
     const float d = f.depth[j];
     if (!(d > 0.0f && d <= FLT_MAX) || (f.mask && f.mask[j] == 0)) return false;
-    *c_z = c[2];
     *pixel = j;
     return true;
-}
-
-__device__ __forceinline__ void node_index(const Grid& g, long long n, int at[3]) {
-    at[0] = (int)(n % g.n[0]);
-    const long long row = n / g.n[0];
-    at[1] = (int)(row % g.n[1]);
-    at[2] = (int)(row / g.n[1]);
 }
 
 // the node index of n's neighbour at offset code `code` (bit 0 = x, bit 1 = y, bit 2 = z)
@@ -349,22 +324,6 @@ struct MeshWorkspace {
     }
 };
 
-// SNERF_OK with *g filled, or the status the call returns (message set)
-int grid_of(const char* what, double voxel_size, double lo_x, double lo_y, double lo_z, int nx, int ny, int nz, Grid* g) {
-    SNERF_REQUIRE(nx >= 1 && ny >= 1 && nz >= 1, "%s: extents %d x %d x %d, each must be at least 1", what, nx, ny, nz);
-    SNERF_REQUIRE(voxel_size > 0.0 && std::isfinite(voxel_size), "%s: voxel_size %g, expected a finite number > 0", what, voxel_size);
-    SNERF_REQUIRE(std::isfinite(lo_x) && std::isfinite(lo_y) && std::isfinite(lo_z), "%s: the bound (%g, %g, %g) is not finite", what, lo_x,
-                  lo_y, lo_z);
-    const long long limit = kMaxCount / kKeysPerNode, xy = (long long)nx * ny;
-    if (xy > limit || xy * nz > limit)
-        return snerf::fail(SNERF_E_UNSUPPORTED, "%s: extents %d x %d x %d exceed the limit 7 nx ny nz <= 2^31 - 1", what, nx, ny, nz);
-    g->voxel_size = voxel_size;
-    g->lo[0] = lo_x; g->lo[1] = lo_y; g->lo[2] = lo_z;
-    g->n[0] = nx; g->n[1] = ny; g->n[2] = nz;
-    g->nodes = xy * nz;
-    return SNERF_OK;
-}
-
 // SNERF_OK with *f's extents filled, or the status the call returns (message set)
 int views_of(const char* what, int views, int height, int width, Views* f) {
     SNERF_REQUIRE(views >= 0 && height >= 0 && width >= 0, "%s: %d views of %d x %d", what, views, height, width);
@@ -378,8 +337,6 @@ int views_of(const char* what, int views, int height, int width, Views* f) {
     f->pixels = pixels;
     return SNERF_OK;
 }
-
-unsigned node_blocks(long long count) { return (unsigned)((count + kBlock - 1) / kBlock); }
 
 int mesh_arguments(const char* what, const float* tsdf, const unsigned char* weight, int min_weight, const long long* counts,
                    const void* workspace) {

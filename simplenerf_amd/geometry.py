@@ -14,9 +14,17 @@ restates them): ``tsdf_volume`` averages truncated signed distances into a regul
 over it (six Kuhn tetrahedra a cell: no ambiguous case, watertight wherever the volume is observed), ``colour_points`` colours the
 vertices from the frames; ``save_ply_mesh`` writes the indexed file.
 
-Out of scope: marching cubes, Poisson reconstruction, normals, bilinear depth lookups, view-angle or distance
-weighting, sparse or hashed volumes, dropping zero-area triangles, welding coincident vertices, two-way reprojection checks, sharding
-over ranks, ASCII PLY, meshing the density field directly.
+The density field is meshed without a render (csrc/field.hip; csrc/simplenerf_field.h states the rules, tests/field_reference.py
+restates them): ``density_volume`` maps the grid's nodes into the space the model's MLP reads (the NDC warp for LLFF models),
+counts the views that see each, asks the field for its densities there and turns them into the signed volume of a density level;
+``extract_mesh`` meshes it as above; ``colour_vertices`` asks the field for the colour of every vertex, seen from the nearest
+camera that sees it.
+
+Out of scope: marching cubes, Poisson reconstruction, normals (from the depth maps or from the field's
+gradient), bilinear depth lookups, view-angle or distance weighting, sparse or hashed volumes, dropping zero-area triangles, welding
+coincident vertices, two-way reprojection checks, sharding over ranks, ASCII PLY; for the density mesh also a density-only forward
+that skips the feature and views layers, empty-space culling, default bounds, and the opacity of a voxel step as the level-set
+quantity.
 """
 from __future__ import annotations
 
@@ -151,6 +159,77 @@ def colour_points(points: Tensor, depth: Tensor, image: Tensor, extrinsics, intr
     uint8 (V,h,w,3) ``image`` pixels it projects to in the views whose valid depth there is within ``colour_tolerance`` (scene units)
     of the point's own depth in that view; ``views`` counts them, and the colour is (0,0,0) where it is 0."""
     return ops.colour_points(points, depth, image, _views_of(depth, extrinsics, intrinsics), colour_tolerance, mask)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the field
+def ndc_parameters(camera: dict):
+    """-> (cx, cy, near) float64: the parameters of the NDC warp of a camera dict as ``harness.frame_batch`` takes it, evaluated as the
+    ray generator evaluates them in fp32: cx = -1 / (W / (2 fx)), cy = -1 / (H / (2 fy)); near is the camera's near plane."""
+    h, w = (int(v) for v in camera['resolution'])
+    intrinsic = numpy.asarray(camera['intrinsic'], dtype=numpy.float64).reshape(3, 3)
+    cx = -1.0 / (float(w) / (2.0 * float(intrinsic[0, 0])))
+    cy = -1.0 / (float(h) / (2.0 * float(intrinsic[1, 1])))
+    return cx, cy, float(camera['near'])
+
+
+def _field_cameras(extrinsics, intrinsics, device):
+    views = len(extrinsics)
+    cameras = fuse_cameras(_matrices(extrinsics, 'extrinsics', (views, 4, 4)), _matrices(intrinsics, 'intrinsics', (views, 3, 3)))
+    return torch.from_numpy(cameras.reshape(views, ops.FUSE_CAMERA)).to(device)
+
+
+def density_volume(query, lo, voxel_size: float, extents, extrinsics, intrinsics, resolution, level: float, ndc=None,
+                   point_block: int = 1 << 20, device=None):
+    """-> (sigma float32, tsdf float32, weight uint8), each (nz,ny,nx) on the device: the density field ``query`` sampled at the
+    nodes of the grid of ``extents`` = (nx,ny,nz) whose node (i,j,k) sits at ``lo`` + ``voxel_size`` (i,j,k), in the scene frame of
+    the (V,4,4) world-to-camera ``extrinsics``.  ``query`` is any callable from float32 (n,3) device points, in the space the model's
+    MLP reads, to float32 (n,) densities; ``ndc`` = (cx, cy, near) (``ndc_parameters``) maps the nodes there for a model of NDC
+    rays, None leaves them as they are.  ``weight`` counts the views that see a node (in front of the view, and projecting inside
+    its (height, width) = ``resolution`` frame); ``tsdf`` = clamp((``level`` - sigma) / ``level``, -1, 1), and 1 where no view sees
+    the node or the density is a NaN: the volume ``extract_mesh`` takes, whose surface is the level set sigma = ``level`` with
+    normals out of the dense side.  The grid is walked in blocks of ``point_block`` nodes; nodes that no view sees are queried too.
+    ``device`` defaults to the current GPU."""
+    level = float(level)
+    if not (level > 0.0 and numpy.isfinite(level)):
+        raise RuntimeError(f'level: expected a finite number > 0, got {level}')
+    if isinstance(point_block, bool) or int(point_block) != point_block or int(point_block) < 1:
+        raise RuntimeError(f'point_block: expected an integer >= 1, got {point_block}')
+    lo, voxel_size, extents = ops.mesh_grid(lo, voxel_size, extents)
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    cameras = _field_cameras(extrinsics, intrinsics, device)
+    nx, ny, nz = extents
+    nodes = nx * ny * nz
+    sigma = torch.empty((nodes,), dtype=torch.float32, device=device)
+    weight = torch.empty((nodes,), dtype=torch.uint8, device=device)
+    for first in range(0, nodes, int(point_block)):
+        count = min(int(point_block), nodes - first)
+        points, weight[first:first + count] = ops.field_grid_points(lo, voxel_size, extents, cameras, resolution, ndc, first, count)
+        values = query(points)
+        if not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or tuple(values.shape) != (count,):
+            raise RuntimeError(f'query: expected float32 densities of shape ({count},), got '
+                               f'{(values.dtype, tuple(values.shape)) if isinstance(values, torch.Tensor) else type(values).__name__}')
+        sigma[first:first + count] = values
+    tsdf = ops.field_values(sigma, weight, level)
+    return sigma.reshape(nz, ny, nx), tsdf.reshape(nz, ny, nx), weight.reshape(nz, ny, nx)
+
+
+def colour_vertices(query, vertices: Tensor, extrinsics, intrinsics, resolution, ndc=None):
+    """-> (colours uint8 (Nv,3), views uint8 (Nv)) on the device: the colour the field gives every float32 (Nv,3) scene-frame vertex,
+    seen from the camera that sees it from the smallest depth; ``views`` is that camera's index, or ``ops.FIELD_NO_VIEW`` where none
+    sees the vertex (camera 0's direction is used).  ``query`` is any callable from (float32 (n,3) points in the MLP's input space,
+    float32 (n,3) unit view directions in the scene frame) to float32 (n,3) colours in [0, 1]; they are converted as
+    ``ops.to_display`` converts a frame."""
+    vertices = ops._typed(vertices, 'vertices', (torch.float32,))
+    cameras = _field_cameras(extrinsics, intrinsics, vertices.device)
+    points, view_dirs, views = ops.field_point_views(vertices, cameras, resolution, ndc)
+    count = int(points.shape[0])
+    if count == 0:
+        return torch.empty((0, 3), dtype=torch.uint8, device=vertices.device), views
+    rgb = query(points, view_dirs)
+    if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.float32 or tuple(rgb.shape) != (count, 3):
+        raise RuntimeError(f'query: expected float32 colours of shape ({count}, 3), got '
+                           f'{(rgb.dtype, tuple(rgb.shape)) if isinstance(rgb, torch.Tensor) else type(rgb).__name__}')
+    return ops.to_display(rgb)[0], views
 
 
 def ply_mesh_bytes(points, colours, triangles) -> bytes:

@@ -1159,6 +1159,65 @@ def export_mesh(model, configs: dict, cameras, path, device, voxel_size: float, 
             'voxel_size': voxel_size, 'extents': extents, 'truncation': truncation, 'images_device': images, 'depths_device': depths}
 
 
+@torch.no_grad()
+def export_density_mesh(model, configs: dict, cameras, path, device, voxel_size: float, level: float, bounds, min_views: int = 1,
+                        point_block: int = 1 << 20) -> dict:
+    """The model's geometry as a triangle mesh of its density field, without a render: the nodes of a grid of ``voxel_size`` over the
+    box ``bounds`` = ((x0, y0, z0), (x1, y1, z1)) (required: there are no depth maps to derive it from; the grid is made as
+    ``export_mesh`` makes it) are mapped into the space the finest MLP reads -- the NDC warp when ``configs['data_loader']['ndc']``,
+    with ``cameras[0]``'s frame, focal lengths and near plane -- and queried (``model.query``, in blocks of ``point_block``); the
+    surface is the level set density = ``level`` (``geometry.density_volume``), extracted by marching tetrahedra over the cells
+    whose eight corners at least ``min_views`` of ``cameras`` see (``geometry.extract_mesh``), every vertex coloured by the field
+    as the nearest camera that sees it would see it (``geometry.colour_vertices``), written to ``path`` as a binary PLY
+    (``geometry.save_ply_mesh``: a file that exists is left alone).  ``cameras`` are dicts as ``frame_batch`` takes them, of one
+    resolution; with NDC they must also share the focal lengths and the near plane.  ``level`` is in the model's OWN density units:
+    density per unit of the length its MLP's rays are marched in -- scene length for a model of world-space rays, NDC length (the
+    whole scene depth is about 1) for a model of NDC rays, where useful levels are therefore far larger.  The mesh is in the model's
+    processed scene frame, also for NDC models.  A ``DataParallel`` wrapper is unwrapped.  Raises, naming the limit
+    7 nx ny nz <= 2^31 - 1, when the grid is too large.  Returns {'vertices' float32 (Nv,3), 'colours' uint8 (Nv,3), 'views' uint8
+    (Nv): the camera each vertex is coloured from (``ops.FIELD_NO_VIEW``: none sees it), 'triangles' int32 (Nt,3), 'sigma', 'tsdf'
+    float32 (nz,ny,nx), 'weight' uint8 (nz,ny,nx), 'lo', 'voxel_size', 'extents' (nx,ny,nz), 'level'}, tensors on the device."""
+    from . import geometry
+    model = getattr(model, 'module', model) if isinstance(model, torch.nn.DataParallel) else model
+    cameras = list(cameras)
+    if not cameras:
+        raise RuntimeError('export_density_mesh: no cameras')
+    voxel_size, level = float(voxel_size), float(level)
+    if not (voxel_size > 0.0 and math.isfinite(voxel_size)):
+        raise RuntimeError(f'export_density_mesh: voxel_size: expected a finite number > 0, got {voxel_size}')
+    if not (level > 0.0 and math.isfinite(level)):
+        raise RuntimeError(f'export_density_mesh: level: expected a finite number > 0, got {level}')
+    mlp = 'fine_mlp' if 'fine_mlp' in configs['model'] else 'coarse_mlp'
+    if bool(configs['model'][mlp].get('predict_visibility', False)):
+        raise NotImplementedError(f'export_density_mesh: {mlp} has predict_visibility, which point queries are not built for')
+    resolution = tuple(int(v) for v in cameras[0]['resolution'])
+    for i, camera in enumerate(cameras):
+        if tuple(int(v) for v in camera['resolution']) != resolution:
+            raise RuntimeError(f'export_density_mesh: camera {i} has resolution {tuple(camera["resolution"])}, camera 0 has {resolution}')
+    ndc = None
+    if bool(configs['data_loader']['ndc']):
+        ndc = geometry.ndc_parameters(cameras[0])
+        for i, camera in enumerate(cameras):
+            if geometry.ndc_parameters(camera) != ndc:
+                raise RuntimeError(f'export_density_mesh: ndc: camera {i} has (cx, cy, near) = {geometry.ndc_parameters(camera)}, camera 0 '
+                                   f'has {ndc}; one NDC warp needs cameras of one resolution, focal length and near plane')
+    low, high = (numpy.asarray(b, dtype=numpy.float64).reshape(3) for b in bounds)
+    if not (numpy.isfinite(low).all() and numpy.isfinite(high).all() and (high >= low).all()):
+        raise RuntimeError(f'export_density_mesh: bounds {low.tolist()} .. {high.tolist()} are not a finite box')
+    extents = tuple(int(math.floor((high[a] - low[a]) / voxel_size)) + 2 for a in range(3))     # (the last node at or past the bound)
+    lo, voxel_size, extents = ops.mesh_grid(low.tolist(), voxel_size, extents)
+    matrices = [geometry.camera_matrices(camera) for camera in cameras]
+    extrinsics, intrinsics = [m[0] for m in matrices], [m[1] for m in matrices]
+    sigma, tsdf, weight = geometry.density_volume(lambda points: model.query(points, None, mlp, point_block)['sigma'], lo, voxel_size,
+                                                  extents, extrinsics, intrinsics, resolution, level, ndc, point_block, device)
+    vertices, triangles = geometry.extract_mesh(tsdf, weight, lo, voxel_size, min_views)
+    colours, views = geometry.colour_vertices(lambda points, dirs: model.query(points, dirs, mlp, point_block)['rgb'], vertices,
+                                              extrinsics, intrinsics, resolution, ndc)
+    geometry.save_ply_mesh(path, vertices, colours, triangles)
+    return {'vertices': vertices, 'colours': colours, 'views': views, 'triangles': triangles, 'sigma': sigma, 'tsdf': tsdf,
+            'weight': weight, 'lo': lo, 'voxel_size': voxel_size, 'extents': extents, 'level': level}
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # the trainer's two frame loops (src/Trainer01.py: run_validation :109-263, save_sample_images :319-350)
 # per-sample outputs the reference deletes from every chunk before merging (:197-221)

@@ -361,6 +361,60 @@ class SimpleNeRFHip(torch.nn.Module):
             self._packed[key] = (stamp, packed)
         return self._packed[key][1]
 
+    @torch.no_grad()
+    def query(self, points: Tensor, view_dirs: Optional[Tensor] = None, mlp: Optional[str] = None, point_block: int = 1 << 20
+              ) -> Dict[str, Tensor]:
+        """The field itself: {'sigma' (N,), 'rgb' (N,3)} of MLP ``mlp`` ('fine_mlp' when the model has one, else 'coarse_mlp') at the
+        float32 (N,3) ``points`` on the GPU, which are ALREADY in the MLP's input space (NDC for a model of NDC rays:
+        ``ops.field_grid_points`` / ``ops.field_point_views`` map scene-frame points there), seen from the unit ``view_dirs`` (N,3).
+        With ``view_dirs`` None a view-dependent MLP is fed (0, 0, -1) -- the density does not depend on it -- and 'rgb' is left
+        out.  Runs under no_grad in blocks of ``point_block`` points at the model's precision, through the weight stream a render
+        packs: every point is a ray of one sample, origin = the point, direction and depth 0, so the kernels form the exact
+        position o + 0 . 0.  A ``predict_visibility`` MLP is refused."""
+        if mlp is None:
+            mlp = 'fine_mlp' if self.fine_mlp_needed else 'coarse_mlp'
+        names = {'coarse_mlp': 'coarse_model', 'fine_mlp': 'fine_model' if self.fine_mlp_needed else None}
+        if names.get(mlp) is None:
+            raise KeyError(f"mlp: expected one of {sorted(k for k, v in names.items() if v)}, got {mlp!r}")
+        module: MlpParameters = getattr(self, names[mlp])
+        if module.predict_visibility:
+            raise NotImplementedError('query: predict_visibility MLPs are not built for point queries (their views head has a fourth '
+                                      'output the forward kernels do not return)')
+        if isinstance(point_block, bool) or int(point_block) != point_block or int(point_block) < 1:
+            raise RuntimeError(f'point_block: expected an integer >= 1, got {point_block}')
+        points = ops._dev(points, 'points')
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise RuntimeError(f'points: expected shape (N, 3), got {tuple(points.shape)}')
+        n = int(points.shape[0])
+        dev = points.device
+        if view_dirs is not None:
+            view_dirs = ops._dev(view_dirs, 'view_dirs', (n, 3))
+            if view_dirs.device != dev:
+                raise RuntimeError(f'view_dirs: expected a tensor on {dev}, got one on {view_dirs.device}')
+        sigma = torch.empty((n,), dtype=torch.float32, device=dev)
+        rgb = torch.empty((n, 3), dtype=torch.float32, device=dev) if view_dirs is not None else None
+        if n > 0:
+            packed = self._packed_mlp(names[mlp], False)
+            block = min(int(point_block), n)
+            zeros = torch.zeros((block, 3), dtype=torch.float32, device=dev)
+            depths = torch.zeros((block, 1), dtype=torch.float32, device=dev)
+            default_dirs = None
+            if view_dirs is None and packed.use_view_dirs:
+                default_dirs = torch.tensor([0.0, 0.0, -1.0], dtype=torch.float32, device=dev).expand(block, 3).contiguous()
+            for first in range(0, n, block):
+                rows = min(block, n - first)
+                dirs = None
+                if packed.use_view_dirs:
+                    dirs = default_dirs[:rows] if view_dirs is None else view_dirs[first:first + rows]
+                s, c = packed.forward(points[first:first + rows], zeros[:rows], dirs, depths[:rows], None, self.precision)
+                sigma[first:first + rows] = s.reshape(rows)
+                if rgb is not None:
+                    rgb[first:first + rows] = c.reshape(rows, 3)
+        out = {'sigma': sigma}
+        if rgb is not None:
+            out['rgb'] = rgb
+        return out
+
     # ------------------------------------------------------------------------------------------
     def _render_with_ctypes(self, batch, draws, present, packed, s_c, s_f, per_sample, with_grad, returns):
         """ops.RenderCall (ctypes over the C ABI) + the Python autograd.Function."""

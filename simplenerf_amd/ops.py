@@ -1312,6 +1312,101 @@ def colour_points(points: Tensor, depth: Tensor, image: Tensor, cameras: Tensor,
     return colours, agreeing
 
 
+# ---------------------------------------------------------------------------------------------- Q8 the field export
+FIELD_NO_VIEW = C.SNERF_FIELD_NO_VIEW     # the view byte of a point that no view sees
+
+
+def _field_views(cameras, resolution, ndc, least: int):
+    """The camera table, frame size and input map of a field call, checked -> (cameras, views, h, w, (flag, cx, cy, near))."""
+    cameras = _typed(cameras, 'cameras', (torch.float64,))
+    if cameras.dim() != 2 or cameras.shape[1] != FUSE_CAMERA:
+        raise RuntimeError(f'cameras: expected shape (views, {FUSE_CAMERA}), got {tuple(cameras.shape)}')
+    views = int(cameras.shape[0])
+    if not least <= views <= FUSE_MAX_VIEWS:
+        raise RuntimeError(f'cameras: {views} views, expected {least}..{FUSE_MAX_VIEWS}')
+    resolution = tuple(resolution)
+    if len(resolution) != 2 or any(isinstance(v, bool) or int(v) != v or int(v) < 0 for v in resolution):
+        raise RuntimeError(f'resolution: expected two integers >= 0 (height, width), got {resolution}')
+    if ndc is None:
+        return cameras, views, int(resolution[0]), int(resolution[1]), (0, 0.0, 0.0, 0.0)
+    ndc = tuple(float(v) for v in ndc)
+    if len(ndc) != 3 or not all(math.isfinite(v) for v in ndc) or not ndc[2] > 0.0:
+        raise RuntimeError(f'ndc: expected None or three finite numbers (cx, cy, near) with near > 0, got {ndc}')
+    return cameras, views, int(resolution[0]), int(resolution[1]), (1,) + ndc
+
+
+def field_grid_points(lo, voxel_size: float, extents, cameras: Tensor, resolution, ndc=None, first_node: int = 0,
+                      count: Optional[int] = None):
+    """-> (mlp_points float32 (count,3), weight uint8 (count)) on the device: for the nodes ``first_node`` .. ``first_node`` + ``count``
+    - 1 of the grid (node (i,j,k), index (k ny + j) nx + i, at ``lo`` + ``voxel_size`` (i,j,k); ``extents`` = (nx,ny,nz); ``count``
+    defaults to the rest of the grid) the point the model's MLP reads and the number of views that see the node: it lies in front
+    of the view and projects (nearest pixel, ties to even) inside the (height, width) = ``resolution`` frame
+    (csrc/simplenerf_field.h has the rules).  ``ndc``: None for a model of world-space rays (the point is the node), or (cx, cy,
+    near) for a model of NDC rays (``geometry.ndc_parameters``): nodes nearer than the near plane get (0,0,0) and weight 0.
+    ``cameras``: float64 (V,42) on the device (``geometry.fuse_cameras``), V >= 0."""
+    lo, voxel_size, extents = mesh_grid(lo, voxel_size, extents)
+    cameras, views, h, w, ndc = _field_views(cameras, resolution, ndc, 0)
+    nodes = extents[0] * extents[1] * extents[2]
+    if isinstance(first_node, bool) or int(first_node) != first_node or not 0 <= int(first_node) <= nodes:
+        raise RuntimeError(f'first_node: expected 0..{nodes}, got {first_node}')
+    first_node = int(first_node)
+    if count is None:
+        count = nodes - first_node
+    if isinstance(count, bool) or int(count) != count or not 0 <= int(count) <= nodes - first_node:
+        raise RuntimeError(f'count: expected 0..{nodes - first_node} (the nodes from first_node on), got {count}')
+    count = int(count)
+    dev = cameras.device
+    points = torch.empty((count, 3), dtype=torch.float32, device=dev)
+    weight = torch.empty((count,), dtype=torch.uint8, device=dev)
+    if count > 0:
+        _enqueue('snerf_field_grid_points', dev, voxel_size, *lo, *extents, first_node, count, _ptr(cameras if views else None), views, h, w,
+                 *ndc, _ptr(points), _ptr(weight))
+    return points, weight
+
+
+def field_point_views(points: Tensor, cameras: Tensor, resolution, ndc=None):
+    """-> (mlp_points float32 (N,3), view_dirs float32 (N,3), view uint8 (N)) on the device: per float32 (N,3) scene-frame point the
+    point the model's MLP reads, the unit direction (scene frame) from the centre of the view that sees it from the smallest depth
+    (the lowest index among equal ones) and that view's index; where no view sees the point, view 0's direction and
+    ``FIELD_NO_VIEW`` (csrc/simplenerf_field.h has the rules).  ``cameras``, ``resolution``, ``ndc`` as ``field_grid_points`` takes
+    them, V >= 1."""
+    points = _typed(points, 'points', (torch.float32,))
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError(f'points: expected shape (N, 3), got {tuple(points.shape)}')
+    n = int(points.shape[0])
+    if n > SORT_MAX_COUNT:
+        raise RuntimeError(f'points: {n} points exceed the 2^31 - 1 the kernels index')
+    cameras, views, h, w, ndc = _field_views(cameras, resolution, ndc, 1)
+    dev = points.device
+    _warp_together(dev, cameras=cameras)
+    mlp_points, view_dirs = torch.empty_like(points), torch.empty_like(points)
+    view = torch.empty((n,), dtype=torch.uint8, device=dev)
+    if n > 0:
+        _enqueue('snerf_field_point_views', dev, _ptr(points), n, _ptr(cameras), views, h, w, *ndc, _ptr(mlp_points), _ptr(view_dirs),
+                 _ptr(view))
+    return mlp_points, view_dirs, view
+
+
+def field_values(sigma: Tensor, weight: Tensor, level: float) -> Tensor:
+    """-> tsdf float32, shaped like ``sigma``, on the device: min(1, max(-1, (``level`` - sigma) / ``level``)) in float64 per element
+    of the float32 ``sigma``, and 1 where the uint8 ``weight`` (same shape) is 0 or sigma is a NaN -- the signed volume
+    ``mesh_extract`` takes, negative on the dense side (csrc/simplenerf_field.h has the rule).  ``level``: a finite number > 0."""
+    sigma = _typed(sigma, 'sigma', (torch.float32,))
+    weight = _typed(weight, 'weight', (torch.uint8,), tuple(sigma.shape))
+    level = float(level)
+    if not (level > 0.0 and math.isfinite(level)):
+        raise RuntimeError(f'level: expected a finite number > 0, got {level}')
+    n = int(sigma.numel())
+    if n > SORT_MAX_COUNT:
+        raise RuntimeError(f'sigma: {n} elements exceed the 2^31 - 1 the kernels index')
+    dev = sigma.device
+    _warp_together(dev, weight=weight)
+    tsdf = torch.empty_like(sigma)
+    if n > 0:
+        _enqueue('snerf_field_values', dev, _ptr(sigma), _ptr(weight), n, level, _ptr(tsdf))
+    return tsdf
+
+
 # ---------------------------------------------------------------------------------------------- f1 losses
 class LossTermSpec:
     """One masked mean-squared-error term of the fused loss evaluation (struct snerf_loss_term).  ``two_sided``: the
