@@ -6,6 +6,8 @@
 // snerf_field_point_views, one launch: a thread per point maps it, picks the nearest view that sees it and writes the unit
 //   direction from that view's centre.
 // snerf_field_values, one launch: a thread per element.
+// snerf_field_normals (simplenerf_gradient.h), one launch: a thread per point pulls the density's MLP-space gradient back through
+//   the input map and writes the unit outward normal.
 // The projection and the grid are mesh.hip's own device functions (mesh_lookup.h).  No atomics, one owner per output element, fp64
 // throughout (the library is built with -ffp-contract=off).
 // Bound: the first two by the fp64 divide rate (two divisions per view and point), the third by memory (9 bytes an element).
@@ -13,6 +15,7 @@
 
 #include "snerf_common.h"
 #include "simplenerf_field.h"
+#include "simplenerf_gradient.h"
 #include "mesh_lookup.h"
 #include "sort_plan.h"
 
@@ -115,6 +118,27 @@ __global__ void __launch_bounds__(kBlock) field_values_kernel(const float* __res
     tsdf[i] = (float)value;
 }
 
+// grid (ceil(count / kBlock)): the MLP-space gradient pulled back through the input map, negated and normalised (simplenerf_gradient.h)
+__global__ void __launch_bounds__(kBlock) field_normals_kernel(const float* __restrict__ points, const float* __restrict__ grad, long long count,
+                                                               InputMap m, float* __restrict__ normals) {
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= count) return;
+    const double P[3] = {(double)points[3 * i], (double)points[3 * i + 1], (double)points[3 * i + 2]};
+    const double g[3] = {(double)grad[3 * i], (double)grad[3 * i + 1], (double)grad[3 * i + 2]};
+    double G[3] = {g[0], g[1], g[2]};
+    bool in_front = true;
+    if (m.ndc) {
+        in_front = P[2] <= -m.near;       // (a NaN is not in front)
+        G[0] = (m.cx / P[2]) * g[0];
+        G[1] = (m.cy / P[2]) * g[1];
+        G[2] = -((((m.cx * P[0]) * g[0] + (m.cy * P[1]) * g[1]) + (2.0 * m.near) * g[2]) / (P[2] * P[2]));
+    }
+    const double n = sqrt((G[0] * G[0] + G[1] * G[1]) + G[2] * G[2]);
+    const bool usable = in_front && n > 0.0 && n < INFINITY;     // (a NaN length fails both comparisons)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) normals[3 * i + a] = usable ? (float)(-G[a] / n) : 0.0f;
+}
+
 // SNERF_OK with *f's extents and *m filled, or the status the call returns (message set)
 int views_of(const char* what, int views, int least, int height, int width, int ndc, double cx, double cy, double near, Cameras* f,
              InputMap* m) {
@@ -182,4 +206,19 @@ extern "C" int snerf_field_values(const float* sigma, const unsigned char* weigh
     SNERF_REQUIRE(sigma && weight && tsdf, "field_values: NULL pointer");
     hipLaunchKernelGGL(field_values_kernel, dim3(node_blocks(count)), dim3(kBlock), 0, (hipStream_t)stream, sigma, weight, count, level, tsdf);
     return snerf::check_launch("field_values");
+}
+
+extern "C" int snerf_field_normals(const float* points_scene, const float* grad_mlp, long long count, int ndc, double cx, double cy, double near,
+                                   float* normals, snerf_stream_t stream) {
+    SNERF_REQUIRE(count >= 0, "field_normals: count %lld", count);
+    Cameras f;
+    InputMap m;
+    const int status = views_of("field_normals", 0, 0, 0, 0, ndc, cx, cy, near, &f, &m);
+    if (status != SNERF_OK) return status;
+    if (count > kMaxCount) return snerf::fail(SNERF_E_UNSUPPORTED, "field_normals: count %lld exceeds 2^31 - 1", count);
+    if (count == 0) return SNERF_OK;
+    SNERF_REQUIRE(points_scene && grad_mlp && normals, "field_normals: NULL pointer");
+    hipLaunchKernelGGL(field_normals_kernel, dim3(node_blocks(count)), dim3(kBlock), 0, (hipStream_t)stream, points_scene, grad_mlp, count, m,
+                       normals);
+    return snerf::check_launch("field_normals");
 }

@@ -1460,3 +1460,92 @@ extern "C" int snerf_mlp_backward(const snerf_mlp_desc* desc, const float* packe
     if (rc != SNERF_OK) return rc;
     return SNERF_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// The gradient with respect to the input point (simplenerf_gradient.h): the clear and the chain above, with a zero page for d_rgb
+// and no weight-gradient launches, then the product with W_0 (and W_5's encoding columns) and the encoding's Jacobian
+// (mlp_input_grad.hip).  Workspace: dY tiles | zero pages and region table as snerf_mlp_backward lays them | 3 . num_points zeros.
+// ------------------------------------------------------------------------------------------------
+namespace snerf {
+int mlp_input_gradient_encoding(const MlpPlan& plan, const float* w0, const float* w5, const float* acts, const float* grads,
+                                long long total, float* d_points, hipStream_t stream);   // mlp_input_grad.hip
+}
+
+namespace {
+
+struct InputGradientWorkspace {
+    long long grads_floats, clear_words, total_floats;
+};
+
+// SNERF_OK with *plan and *ws filled, or the status snerf_mlp_input_gradient returns for this descriptor and count (message set)
+int input_gradient_plan(const snerf_mlp_desc* desc, long long num_points, snerf::MlpPlan* plan, InputGradientWorkspace* ws) {
+    const int st = snerf::build_plan(desc, plan);
+    snerf::GenericPlan layered;
+    if (st == SNERF_E_UNSUPPORTED && snerf::generic_takes(desc, &layered))
+        return snerf::fail(SNERF_E_UNSUPPORTED, "mlp_input_gradient: built for the fused MLP shapes only (width 256 with views width 128, "
+                           "width 128 with views width 64, or without a views layer), not for the layered path's shapes");
+    if (st != SNERF_OK) return st;
+    if (desc->predict_visibility)
+        return snerf::fail(SNERF_E_UNSUPPORTED, "mlp_input_gradient: not built for predict_visibility MLPs");
+    const int key = plan->wt * 10 + plan->vt;
+    if (key != 84 && key != 80 && key != 42 && key != 40)
+        return snerf::fail(SNERF_E_UNSUPPORTED, "mlp_input_gradient: width %d / views width %d not built", plan->width, plan->views_width);
+    SNERF_REQUIRE(num_points >= 1, "mlp_input_gradient: bad size num_points=%lld", num_points);
+    const long long table_words = kRegionTableFloat0 + kRegionSlots * kRegionWords;
+    if ((num_points + 127) / 128 > 0x7fffffffLL || table_words + 3 * num_points > 0x7fffffffLL)
+        return snerf::fail(SNERF_E_UNSUPPORTED, "mlp_input_gradient: too many points (%lld)", num_points);
+    ws->grads_floats = (num_points + 127) / 128 * 4 * plan->grad_rows() * 32;
+    ws->clear_words = table_words + 3 * num_points;
+    ws->total_floats = ws->grads_floats + ws->clear_words;
+    return SNERF_OK;
+}
+
+}  // namespace
+
+extern "C" size_t snerf_mlp_input_gradient_workspace_floats(const snerf_mlp_desc* desc, long long num_points) {
+    snerf::MlpPlan plan;
+    InputGradientWorkspace ws;
+    if (input_gradient_plan(desc, num_points, &plan, &ws) != SNERF_OK) return 0;
+    return (size_t)ws.total_floats;
+}
+
+extern "C" int snerf_mlp_input_gradient(const snerf_mlp_desc* desc, const float* packed, const float* const* params, int num_params,
+                                        const float* saved_acts, const float* sigma, const float* d_sigma, long long num_points,
+                                        float* workspace, float* d_points, snerf_stream_t stream) {
+    snerf::MlpPlan plan;
+    InputGradientWorkspace ws;
+    const int st = input_gradient_plan(desc, num_points, &plan, &ws);
+    if (st != SNERF_OK) return st;
+    SNERF_REQUIRE(packed && params && saved_acts && sigma && d_sigma && workspace && d_points, "mlp_input_gradient: NULL pointer");
+    SNERF_REQUIRE(num_params == plan.num_params, "mlp_input_gradient: expected %d parameter tensors, got %d", plan.num_params, num_params);
+    const bool skip = plan.depth > 5;
+    SNERF_REQUIRE(params[0] && (!skip || params[10]), "mlp_input_gradient: parameter tensor %d is NULL", params[0] ? 10 : 0);
+    {   // the chain reads the transposed weight stream of the fp32 training layout (snerf_common.h)
+        const int formats = snerf::packed_formats_require(packed, snerf::packed_formats_needed(SNERF_PRECISION_FP32, true), "mlp_input_gradient");
+        if (formats != SNERF_OK) return formats;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    float* grads = workspace;
+    float* partial = workspace + ws.grads_floats;
+    const float* zeros = partial + kRegionTableFloat0 + kRegionSlots * kRegionWords;     // (num_points, 3): d_rgb, and a finite rgb
+    ChainArgs a;
+    a.packed = packed; a.acts = saved_acts; a.sigma = sigma; a.rgb = zeros; a.d_sigma = d_sigma; a.d_rgb = zeros;
+    a.grads = grads; a.total = num_points; a.depth = plan.depth; a.width = plan.width;
+    a.dgrad_offset = plan.dgrad_offset; a.pts_out_w = plan.pts_out_w(); a.views_out_w = plan.views_out_w();
+    a.act_rows = plan.act_rows(); a.act_h1 = plan.act_h(1); a.act_hv = plan.act_hv(); a.act_mask = plan.act_mask();
+    a.grad_rows = plan.grad_rows(); a.grad_feature = plan.grad_feature(); a.grad_yv = plan.grad_yv();
+    a.grad_head = plan.grad_head();
+    a.dy_max = nullptr;
+    hipLaunchKernelGGL(clear_words_kernel, dim3(snerf::stride_grid(ws.clear_words, 256)), dim3(256), 0, s,
+                       reinterpret_cast<unsigned*>(partial), (int)ws.clear_words);
+    int rc = snerf::check_launch("mlp_input_gradient(clear)");
+    if (rc != SNERF_OK) return rc;
+    switch (plan.wt * 10 + plan.vt) {
+        case 84: rc = launch_chain<8, 4, true>(a, s); break;
+        case 80: rc = launch_chain<8, 4, false>(a, s); break;
+        case 42: rc = launch_chain<4, 2, true>(a, s); break;
+        default: rc = launch_chain<4, 2, false>(a, s); break;
+    }
+    if (rc != SNERF_OK) return rc;
+    return snerf::mlp_input_gradient_encoding(plan, params[0], skip ? params[10] : nullptr, saved_acts, grads, num_points, d_points, s);
+}

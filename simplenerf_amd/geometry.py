@@ -20,11 +20,14 @@ counts the views that see each, asks the field for its densities there and turns
 ``extract_mesh`` meshes it as above; ``colour_vertices`` asks the field for the colour of every vertex, seen from the nearest
 camera that sees it.
 
-Out of scope: marching cubes, Poisson reconstruction, normals (from the depth maps or from the field's
-gradient), bilinear depth lookups, view-angle or distance weighting, sparse or hashed volumes, dropping zero-area triangles, welding
-coincident vertices, two-way reprojection checks, sharding over ranks, ASCII PLY; for the density mesh also a density-only forward
-that skips the feature and views layers, empty-space culling, default bounds, and the opacity of a voxel step as the level-set
-quantity.
+``field_normals`` gives the density mesh's vertices the unit outward normals of the field's own gradient (``model.query_gradient``;
+csrc/simplenerf_gradient.h), which ``save_ply_mesh(..., normals=)`` writes.
+
+Out of scope: marching cubes, Poisson reconstruction, normals from the depth maps (for ``export_mesh`` and
+``export_point_cloud``), bilinear depth lookups, view-angle or distance weighting, sparse or hashed volumes, dropping zero-area
+triangles, welding coincident vertices, two-way reprojection checks, sharding over ranks, ASCII PLY; for the density mesh also a
+density-only forward that skips the feature and views layers, empty-space culling, default bounds, the opacity of a voxel step as
+the level-set quantity, and gradients in the 16-bit modes, for layered MLP shapes and of the colour.
 """
 from __future__ import annotations
 
@@ -232,9 +235,39 @@ def colour_vertices(query, vertices: Tensor, extrinsics, intrinsics, resolution,
     return ops.to_display(rgb)[0], views
 
 
-def ply_mesh_bytes(points, colours, triangles) -> bytes:
+def field_normals(query_gradient, vertices: Tensor, ndc=None) -> Tensor:
+    """-> normals float32 (Nv,3) on the device: the unit outward normal of the density field at every float32 (Nv,3) scene-frame
+    vertex, from the field's own gradient instead of the triangles (whose facets carry the pattern of the six tetrahedra).
+    ``query_gradient`` is any callable from float32 (n,3) device points, in the space the model's MLP reads, to the float32 (n,3)
+    gradient of the density there (``lambda p: model.query_gradient(p)['grad']``); ``ndc`` = (cx, cy, near) maps the vertices there
+    for a model of NDC rays, as ``density_volume`` maps the nodes, and the gradient is pulled back through that map
+    (``ops.field_normals``).  (0, 0, 0) where the gradient is zero or not finite, or the vertex is nearer than the near plane."""
+    vertices = ops._typed(vertices, 'vertices', (torch.float32,))
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise RuntimeError(f'vertices: expected shape (Nv, 3), got {tuple(vertices.shape)}')
+    count = int(vertices.shape[0])
+    if count == 0:
+        return torch.empty((0, 3), dtype=torch.float32, device=vertices.device)
+    points = vertices
+    if ndc is not None:       # (the input map alone: one camera row that is never looked at, frames without pixels)
+        cameras = torch.zeros((1, ops.FUSE_CAMERA), dtype=torch.float64, device=vertices.device)
+        points = ops.field_point_views(vertices, cameras, (0, 0), ndc)[0]
+    grad = query_gradient(points)
+    if not isinstance(grad, torch.Tensor) or grad.dtype != torch.float32 or tuple(grad.shape) != (count, 3):
+        raise RuntimeError(f'query_gradient: expected float32 gradients of shape ({count}, 3), got '
+                           f'{(grad.dtype, tuple(grad.shape)) if isinstance(grad, torch.Tensor) else type(grad).__name__}')
+    return ops.field_normals(vertices, grad, ndc)
+
+
+PLY_VERTEX_NORMAL = numpy.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4'),
+                                 ('red', 'u1'), ('green', 'u1'), ('blue', 'u1')])
+
+
+def ply_mesh_bytes(points, colours, triangles, normals=None) -> bytes:
     """A binary little-endian PLY file of N vertices as ``ply_bytes`` writes them and F faces: ``property list uchar int
-    vertex_indices``, 13 bytes a face.  ``triangles`` (F,3) int32, a tensor (copied to the host) or numpy; F = 0 and N = 0 are valid."""
+    vertex_indices``, 13 bytes a face.  ``triangles`` (F,3) int32, a tensor (copied to the host) or numpy; F = 0 and N = 0 are valid.
+    With ``normals`` (N,3) float32 the vertex element is ``x y z nx ny nz red green blue``, 27 bytes a vertex; without, the file is
+    what it was before normals existed."""
     if isinstance(triangles, torch.Tensor):
         triangles = triangles.detach().cpu().numpy()
     triangles = numpy.asarray(triangles)
@@ -243,6 +276,22 @@ def ply_mesh_bytes(points, colours, triangles) -> bytes:
     vertex_file = ply_bytes(points, colours)
     end = b'end_header\n'
     header, records = vertex_file.split(end, 1)
+    if normals is not None:
+        if isinstance(normals, torch.Tensor):
+            normals = normals.detach().cpu().numpy()
+        normals = numpy.asarray(normals)
+        plain = numpy.frombuffer(records, dtype=PLY_VERTEX)
+        if normals.dtype != numpy.float32 or normals.shape != (plain.shape[0], 3):
+            raise RuntimeError(f'normals: expected float32 {(plain.shape[0], 3)}, got {normals.dtype} {normals.shape}')
+        with_normals = numpy.empty(plain.shape, dtype=PLY_VERTEX_NORMAL)
+        for name in PLY_VERTEX.names:
+            with_normals[name] = plain[name]
+        for a, name in enumerate(('nx', 'ny', 'nz')):
+            with_normals[name] = normals[:, a]
+        records = with_normals.tobytes()
+        colour_properties = b'property uchar red\n'
+        before, after = header.split(colour_properties, 1)
+        header = before + b'property float nx\nproperty float ny\nproperty float nz\n' + colour_properties + after
     faces = numpy.empty((triangles.shape[0],), dtype=PLY_FACE)
     faces['count'] = 3
     for a, name in enumerate(('a', 'b', 'c')):
@@ -251,12 +300,12 @@ def ply_mesh_bytes(points, colours, triangles) -> bytes:
             + faces.tobytes())
 
 
-def save_ply_mesh(path, points, colours, triangles) -> None:
+def save_ply_mesh(path, points, colours, triangles, normals=None) -> None:
     """``ply_mesh_bytes`` written to ``path``.  A file that exists is left alone, as ``save_ply`` leaves it."""
     path = os.fspath(path)
     if os.path.exists(path):
         return
-    data = ply_mesh_bytes(points, colours, triangles)
+    data = ply_mesh_bytes(points, colours, triangles, normals)
     os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
     with open(path, 'wb') as f:
         f.write(data)

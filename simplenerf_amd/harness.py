@@ -1161,7 +1161,7 @@ def export_mesh(model, configs: dict, cameras, path, device, voxel_size: float, 
 
 @torch.no_grad()
 def export_density_mesh(model, configs: dict, cameras, path, device, voxel_size: float, level: float, bounds, min_views: int = 1,
-                        point_block: int = 1 << 20) -> dict:
+                        point_block: int = 1 << 20, normals: bool = False) -> dict:
     """The model's geometry as a triangle mesh of its density field, without a render: the nodes of a grid of ``voxel_size`` over the
     box ``bounds`` = ((x0, y0, z0), (x1, y1, z1)) (required: there are no depth maps to derive it from; the grid is made as
     ``export_mesh`` makes it) are mapped into the space the finest MLP reads -- the NDC warp when ``configs['data_loader']['ndc']``,
@@ -1176,7 +1176,10 @@ def export_density_mesh(model, configs: dict, cameras, path, device, voxel_size:
     processed scene frame, also for NDC models.  A ``DataParallel`` wrapper is unwrapped.  Raises, naming the limit
     7 nx ny nz <= 2^31 - 1, when the grid is too large.  Returns {'vertices' float32 (Nv,3), 'colours' uint8 (Nv,3), 'views' uint8
     (Nv): the camera each vertex is coloured from (``ops.FIELD_NO_VIEW``: none sees it), 'triangles' int32 (Nt,3), 'sigma', 'tsdf'
-    float32 (nz,ny,nx), 'weight' uint8 (nz,ny,nx), 'lo', 'voxel_size', 'extents' (nx,ny,nz), 'level'}, tensors on the device."""
+    float32 (nz,ny,nx), 'weight' uint8 (nz,ny,nx), 'lo', 'voxel_size', 'extents' (nx,ny,nz), 'level'}, tensors on the device.
+    ``normals=True`` adds 'normals' float32 (Nv,3), the unit outward normals from the field's own gradient at the vertices
+    (``model.query_gradient``, always fp32, in its own blocks of at most 2^16 points; ``geometry.field_normals``), in the scene
+    frame, and the file's vertices carry them (``x y z nx ny nz red green blue``); the default writes the same bytes as before."""
     from . import geometry
     model = getattr(model, 'module', model) if isinstance(model, torch.nn.DataParallel) else model
     cameras = list(cameras)
@@ -1213,9 +1216,15 @@ def export_density_mesh(model, configs: dict, cameras, path, device, voxel_size:
     vertices, triangles = geometry.extract_mesh(tsdf, weight, lo, voxel_size, min_views)
     colours, views = geometry.colour_vertices(lambda points, dirs: model.query(points, dirs, mlp, point_block)['rgb'], vertices,
                                               extrinsics, intrinsics, resolution, ndc)
-    geometry.save_ply_mesh(path, vertices, colours, triangles)
-    return {'vertices': vertices, 'colours': colours, 'views': views, 'triangles': triangles, 'sigma': sigma, 'tsdf': tsdf,
-            'weight': weight, 'lo': lo, 'voxel_size': voxel_size, 'extents': extents, 'level': level}
+    out = {'vertices': vertices, 'colours': colours, 'views': views, 'triangles': triangles, 'sigma': sigma, 'tsdf': tsdf,
+           'weight': weight, 'lo': lo, 'voxel_size': voxel_size, 'extents': extents, 'level': level}
+    if normals:
+        gradient_block = min(int(point_block), 1 << 16)       # (a gradient block holds ~20 KB a point)
+        out['normals'] = geometry.field_normals(lambda points: model.query_gradient(points, mlp, gradient_block)['grad'], vertices, ndc)
+        geometry.save_ply_mesh(path, vertices, colours, triangles, out['normals'])
+    else:
+        geometry.save_ply_mesh(path, vertices, colours, triangles)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------

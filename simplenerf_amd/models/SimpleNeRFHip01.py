@@ -415,6 +415,67 @@ class SimpleNeRFHip(torch.nn.Module):
             out['rgb'] = rgb
         return out
 
+    @torch.no_grad()
+    def query_gradient(self, points: Tensor, mlp: Optional[str] = None, point_block: int = 1 << 16) -> Dict[str, Tensor]:
+        """The density and its gradient with respect to the point: {'sigma' (N,), 'grad' (N,3)} of MLP ``mlp`` at the float32 (N,3)
+        ``points`` on the GPU, which are ALREADY in the MLP's input space, as ``query`` takes them; 'grad' is d sigma / d point in
+        that space (``ops.field_normals`` pulls it back to the scene frame).  Same arguments, checks and refusals as ``query``.
+        ALWAYS evaluated in fp32 on the master weights, whatever the model's ``hip_precision``, through a weight stream of its own
+        packed for (fp32, training): the normal is a property of the field, and only the fp32 backward chain keeps fp32 dY tiles
+        to carry on through the first layer and the encoding -- so 'sigma' here is the fp32 density, which a 16-bit model's
+        ``query`` only approximates.  Runs under no_grad: the storing forward, the backward chain without its weight-gradient
+        launches, and the input-gradient kernel (csrc/mlp_input_grad.hip), in blocks of ``point_block`` points.  The default block
+        is smaller than ``query``'s because a block holds its saved activations and its dY tiles, about 20 KB a point (1.3 GB at
+        2^16 points of the 8 x 256 MLP).  The gradient is exact where it exists: it jumps where a hidden unit's pre-activation
+        crosses 0, and is (0, 0, 0) where sigma == 0.  A ``predict_visibility`` MLP is refused, and so is an MLP of the layered
+        path's shapes (NotImplementedError naming the limit)."""
+        if mlp is None:
+            mlp = 'fine_mlp' if self.fine_mlp_needed else 'coarse_mlp'
+        names = {'coarse_mlp': 'coarse_model', 'fine_mlp': 'fine_model' if self.fine_mlp_needed else None}
+        if names.get(mlp) is None:
+            raise KeyError(f"mlp: expected one of {sorted(k for k, v in names.items() if v)}, got {mlp!r}")
+        module: MlpParameters = getattr(self, names[mlp])
+        if module.predict_visibility:
+            raise NotImplementedError('query_gradient: predict_visibility MLPs are not built for point queries (their views head has '
+                                      'a fourth output the forward kernels do not return)')
+        if isinstance(point_block, bool) or int(point_block) != point_block or int(point_block) < 1:
+            raise RuntimeError(f'point_block: expected an integer >= 1, got {point_block}')
+        points = ops._dev(points, 'points')
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise RuntimeError(f'points: expected shape (N, 3), got {tuple(points.shape)}')
+        n = int(points.shape[0])
+        dev = points.device
+        sigma = torch.empty((n,), dtype=torch.float32, device=dev)
+        grad = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        if n > 0:
+            params = module.abi_params()
+            # a stream of its own, packed for (fp32, training): the model's render stream keeps its precision and mode
+            stamp = (params[0].data_ptr(),) + tuple(p._version for p in params)
+            cache = self.__dict__.setdefault('_packed_gradient', {})
+            key = (names[mlp], params[0].device)
+            entry = cache.get(key)
+            if entry is None or entry[0] != stamp:
+                packed = entry[1] if entry is not None else ops.PackedMlp(module.mlp_configs, params[0].device)
+                packed.input_gradient_workspace_floats(1)       # (a layered shape is refused before anything is packed)
+                packed.pack(params, ops.PRECISION_FP32, True)
+                cache[key] = (stamp, packed)
+            packed = cache[key][1]
+            block = min(int(point_block), n)
+            zeros = torch.zeros((block, 3), dtype=torch.float32, device=dev)
+            depths = torch.zeros((block, 1), dtype=torch.float32, device=dev)
+            ones = torch.ones((block,), dtype=torch.float32, device=dev)
+            work = torch.empty(packed.input_gradient_workspace_floats(block), dtype=torch.float32, device=dev)
+            dirs = None
+            if packed.use_view_dirs:
+                dirs = torch.tensor([0.0, 0.0, -1.0], dtype=torch.float32, device=dev).expand(block, 3).contiguous()
+            for first in range(0, n, block):
+                rows = min(block, n - first)
+                s, _, saved = packed.forward_train(points[first:first + rows], zeros[:rows], None if dirs is None else dirs[:rows],
+                                                   depths[:rows], None, ops.PRECISION_FP32)
+                sigma[first:first + rows] = s.reshape(rows)
+                grad[first:first + rows] = packed.input_gradient(params, saved, s, ones[:rows], work)
+        return {'sigma': sigma, 'grad': grad}
+
     # ------------------------------------------------------------------------------------------
     def _render_with_ctypes(self, batch, draws, present, packed, s_c, s_f, per_sample, with_grad, returns):
         """ops.RenderCall (ctypes over the C ABI) + the Python autograd.Function."""

@@ -300,6 +300,52 @@ class PackedMlp:
         _lib.check(st, 'snerf_mlp_backward')
         return grads
 
+    def input_gradient_workspace_floats(self, n: int) -> int:
+        """Floats of scratch ``input_gradient`` needs for ``n`` points; raises NotImplementedError, naming the limit, for an MLP the
+        call is not built for (a layered shape, ``predict_visibility``)."""
+        lib = _lib.load()
+        need = int(lib.snerf_mlp_input_gradient_workspace_floats(ctypes.byref(self.desc), int(n)))
+        if need == 0:
+            msg = lib.snerf_last_error()
+            raise NotImplementedError(msg.decode() if msg else 'mlp_input_gradient: not built for this MLP')
+        return need
+
+    def input_gradient(self, params: List[Tensor], saved: Tensor, sigma: Tensor, d_sigma: Optional[Tensor] = None,
+                       work: Optional[Tensor] = None) -> Tensor:
+        """-> float32 (n,3): ``d_sigma`` . d sigma / d point for the n points of a ``forward_train(points, zeros, view_dirs, zeros
+        (n,1), None, PRECISION_FP32)`` call that returned ``sigma`` (n,1,1) and ``saved`` (snerf_mlp_input_gradient,
+        csrc/simplenerf_gradient.h).  ``params``: the tensors this stream was packed from (C-ABI order), with
+        ``pack(params, PRECISION_FP32, training=True)``; the first layer's and the skip layer's weights are read from them.
+        ``d_sigma`` (n,) defaults to ones: the plain gradient.  fp32 and the fused MLP shapes only.  ``work``: the caller's scratch
+        (at least ``input_gradient_workspace_floats(n)`` floats) instead of a fresh allocation."""
+        lib = _lib.load()
+        if len(params) != self.num_params:
+            raise RuntimeError(f'expected {self.num_params} parameter tensors, got {len(params)}')
+        held = [_dev(p, f'param[{i}]') for i, p in enumerate(params)]
+        n = int(sigma.numel())
+        dev = sigma.device
+        sigma = _dev(sigma.reshape(n), 'sigma', (n,))
+        saved = _dev(saved, 'saved')
+        d_sigma = torch.ones((n,), dtype=torch.float32, device=dev) if d_sigma is None else _dev(d_sigma.reshape(-1), 'd_sigma', (n,))
+        _warp_together(dev, saved=saved, d_sigma=d_sigma, buffer=self.buffer, **{f'param[{i}]': p for i, p in enumerate(held)})
+        out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        need = self.input_gradient_workspace_floats(max(n, 1))
+        if n == 0:
+            return out
+        have = int(lib.snerf_mlp_saved_floats(ctypes.byref(self.desc), n, 1))
+        if saved.numel() < have:
+            raise RuntimeError(f'saved: expected the {have} floats forward_train keeps for {n} points, got {saved.numel()}')
+        if work is None:
+            work = torch.empty(need, dtype=torch.float32, device=dev)
+        elif work.dtype != torch.float32 or not work.is_cuda or not work.is_contiguous() or work.numel() < need or work.device != dev:
+            raise RuntimeError(f'input_gradient(work=...): expected a contiguous float32 tensor of at least {need} floats on {dev}')
+        arr = (ctypes.c_void_p * len(held))(*[p.data_ptr() for p in held])
+        with torch.cuda.device(dev):
+            st = lib.snerf_mlp_input_gradient(ctypes.byref(self.desc), _ptr(self.buffer), arr, len(held), _ptr(saved), _ptr(sigma),
+                                              _ptr(d_sigma), n, _ptr(work), _ptr(out), _stream())
+        _lib.check(st, 'snerf_mlp_input_gradient')
+        return out
+
 
 # ---------------------------------------------------------------------------------------------- one-call render ops
 PER_SAMPLE_BITS = {'alpha': 1, 'visibility': 2, 'weights': 4}     # the per-sample request mask of snerf_render_layout_query
@@ -1405,6 +1451,34 @@ def field_values(sigma: Tensor, weight: Tensor, level: float) -> Tensor:
     if n > 0:
         _enqueue('snerf_field_values', dev, _ptr(sigma), _ptr(weight), n, level, _ptr(tsdf))
     return tsdf
+
+
+def field_normals(points: Tensor, grad: Tensor, ndc=None) -> Tensor:
+    """-> float32 (N,3) on the device: the unit outward normal of the density field at every float32 (N,3) scene-frame point, from
+    the float32 (N,3) gradient ``grad`` of the density in the space the model's MLP reads (``PackedMlp.input_gradient``,
+    ``model.query_gradient``): the gradient is pulled back through the input map (``ndc`` = None: the identity; (cx, cy, near): the
+    transposed Jacobian of the NDC warp), negated -- the density's low side is outside -- and normalised, in float64
+    (csrc/simplenerf_gradient.h has the rule).  (0, 0, 0) where the gradient is zero or not finite, or the point is nearer than
+    the near plane."""
+    points = _typed(points, 'points', (torch.float32,))
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError(f'points: expected shape (N, 3), got {tuple(points.shape)}')
+    n = int(points.shape[0])
+    grad = _typed(grad, 'grad', (torch.float32,), (n, 3))
+    if n > SORT_MAX_COUNT:
+        raise RuntimeError(f'points: {n} points exceed the 2^31 - 1 the kernels index')
+    flag = (0, 0.0, 0.0, 0.0)
+    if ndc is not None:
+        ndc = tuple(float(v) for v in ndc)
+        if len(ndc) != 3 or not all(math.isfinite(v) for v in ndc) or not ndc[2] > 0.0:
+            raise RuntimeError(f'ndc: expected None or three finite numbers (cx, cy, near) with near > 0, got {ndc}')
+        flag = (1,) + ndc
+    dev = points.device
+    _warp_together(dev, grad=grad)
+    normals = torch.empty_like(points)
+    if n > 0:
+        _enqueue('snerf_field_normals', dev, _ptr(points), _ptr(grad), n, *flag, _ptr(normals))
+    return normals
 
 
 # ---------------------------------------------------------------------------------------------- f1 losses
