@@ -15,7 +15,7 @@ from .build import INCLUDE
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libsimplenerf_hip.so')
 
-# The headers are the binding's only source (the two under include/, then ADDED_HEADERS, SWEEP_HEADERS, SWEEP16_HEADERS, PNG_HEADERS, JPEG_HEADERS, FUSE_HEADERS, MESH_HEADERS, FIELD_HEADERS and GRADIENT_HEADERS below): every prototype, struct layout, #define and enumerator below is read from them
+# The headers are the binding's only source (the two under include/, then ADDED_HEADERS, SWEEP_HEADERS, SWEEP16_HEADERS, PNG_HEADERS, JPEG_HEADERS, FUSE_HEADERS, MESH_HEADERS, FIELD_HEADERS, GRADIENT_HEADERS and NORMALS_HEADERS below): every prototype, struct layout, #define and enumerator below is read from them
 # (_cdecl.py), in inclusion order.  snerf_iteration records live in pinned host and device memory and are passed by address.
 HEADERS = ('simplenerf_hip.h', 'simplenerf_train.h')
 _decls = _cdecl.Header(by_address=('snerf_iteration',))
@@ -88,6 +88,13 @@ for _name in GRADIENT_HEADERS:
     with open(_name) as _f:
         _decls.read(_f.read(), os.path.basename(_name))
 GRADIENT_SIGNATURES = {_name: _sig for _name, _sig in _decls.functions.items() if _name not in _earlier}
+# The normal maps (csrc/simplenerf_normals.h): an eleventh group, read after the others and bound with them.
+NORMALS_HEADERS = (os.path.join(_HERE, 'csrc', 'simplenerf_normals.h'),)
+_earlier = set(_decls.functions)
+for _name in NORMALS_HEADERS:
+    with open(_name) as _f:
+        _decls.read(_f.read(), os.path.basename(_name))
+NORMALS_SIGNATURES = {_name: _sig for _name, _sig in _decls.functions.items() if _name not in _earlier}
 C = types.SimpleNamespace(**_decls.constants)      # (again: with the #defines of the headers read after the first two)
 ABI_VERSION = C.SNERF_ABI_VERSION
 RENDER_LEVELS, CAMERA_FLOATS = C.SNERF_RENDER_LEVELS, C.SNERF_CAMERA_FLOATS
@@ -117,7 +124,7 @@ def load() -> ctypes.CDLL:
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**SIGNATURES, **ADDED_SIGNATURES, **SWEEP_SIGNATURES, **SWEEP16_SIGNATURES,
                                       **PNG_SIGNATURES, **JPEG_SIGNATURES, **FUSE_SIGNATURES, **MESH_SIGNATURES, **FIELD_SIGNATURES,
-                                      **GRADIENT_SIGNATURES}.items():
+                                      **GRADIENT_SIGNATURES, **NORMALS_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

@@ -17,38 +17,19 @@
 #include "simplenerf_field.h"
 #include "simplenerf_gradient.h"
 #include "mesh_lookup.h"
+#include "field_map.h"
 #include "sort_plan.h"
 
 namespace {
 
 using namespace snerf::sortplan;
 using namespace snerf::mesh;
+using namespace snerf::fieldmap;      // THE INPUT MAP and its pull-back: shared with normals.hip
 
 struct Cameras {
     const double* table;
     int views, height, width;       // views == 0 when the frames have no pixel
 };
-
-struct InputMap {
-    int ndc;
-    double cx, cy, near;
-};
-
-// THE INPUT MAP: Q of P, and whether P is in front (always, without ndc)
-__device__ __forceinline__ bool input_point(const InputMap& m, const double P[3], double Q[3]) {
-    if (!m.ndc) {
-        Q[0] = P[0]; Q[1] = P[1]; Q[2] = P[2];
-        return true;
-    }
-    if (!(P[2] <= -m.near)) {       // (a NaN is not in front)
-        Q[0] = 0.0; Q[1] = 0.0; Q[2] = 0.0;
-        return false;
-    }
-    Q[0] = (m.cx * P[0]) / P[2];
-    Q[1] = (m.cy * P[1]) / P[2];
-    Q[2] = 1.0 + (2.0 * m.near) / P[2];
-    return true;
-}
 
 // grid (ceil(count / kBlock))
 __global__ void __launch_bounds__(kBlock) field_grid_points_kernel(Grid g, long long first_node, long long count, Cameras f, InputMap m,
@@ -125,16 +106,9 @@ __global__ void __launch_bounds__(kBlock) field_normals_kernel(const float* __re
     if (i >= count) return;
     const double P[3] = {(double)points[3 * i], (double)points[3 * i + 1], (double)points[3 * i + 2]};
     const double g[3] = {(double)grad[3 * i], (double)grad[3 * i + 1], (double)grad[3 * i + 2]};
-    double G[3] = {g[0], g[1], g[2]};
-    bool in_front = true;
-    if (m.ndc) {
-        in_front = P[2] <= -m.near;       // (a NaN is not in front)
-        G[0] = (m.cx / P[2]) * g[0];
-        G[1] = (m.cy / P[2]) * g[1];
-        G[2] = -((((m.cx * P[0]) * g[0] + (m.cy * P[1]) * g[1]) + (2.0 * m.near) * g[2]) / (P[2] * P[2]));
-    }
-    const double n = sqrt((G[0] * G[0] + G[1] * G[1]) + G[2] * G[2]);
-    const bool usable = in_front && n > 0.0 && n < INFINITY;     // (a NaN length fails both comparisons)
+    double G[3], n;
+    const bool in_front = pull_back(m, P, g, G);
+    const bool usable = usable_length(G, &n) && in_front;
 #pragma unroll
     for (int a = 0; a < 3; ++a) normals[3 * i + a] = usable ? (float)(-G[a] / n) : 0.0f;
 }

@@ -21,13 +21,21 @@ counts the views that see each, asks the field for its densities there and turns
 camera that sees it.
 
 ``field_normals`` gives the density mesh's vertices the unit outward normals of the field's own gradient (``model.query_gradient``;
-csrc/simplenerf_gradient.h), which ``save_ply_mesh(..., normals=)`` writes.
+csrc/simplenerf_gradient.h), which ``save_ply_mesh(..., normals=)`` and ``save_ply(..., normals=)`` write; the depth mesh's
+vertices and the fused cloud's points take the same normals.
 
-Out of scope: marching cubes, Poisson reconstruction, normals from the depth maps (for ``export_mesh`` and
-``export_point_cloud``), bilinear depth lookups, view-angle or distance weighting, sparse or hashed volumes, dropping zero-area
-triangles, welding coincident vertices, two-way reprojection checks, sharding over ranks, ASCII PLY; for the density mesh also a
-density-only forward that skips the feature and views layers, empty-space culling, default bounds, the opacity of a voxel step as
-the level-set quantity, and gradients in the 16-bit modes, for layered MLP shapes and of the colour.
+A rendered frame has two normal maps (csrc/normals.hip; csrc/simplenerf_normals.h states the rules, tests/normals_reference.py
+restates them): ``ray_normals`` composites the field's normals along every ray with the render's own weights, over the samples that
+carry weight; ``depth_normals`` differences the points of neighbouring pixels of the depth map; ``normals_to_u8`` makes either a
+picture.  Where the two disagree the geometry is not a surface yet.
+
+Out of scope: marching cubes, Poisson reconstruction, bilinear depth lookups, view-angle or distance
+weighting, sparse or hashed volumes, dropping zero-area triangles, welding coincident vertices, two-way reprojection checks,
+sharding over ranks, ASCII PLY; for the density mesh also a density-only forward that skips the feature and views layers,
+empty-space culling, default bounds, the opacity of a voxel step as the level-set quantity, and gradients in the 16-bit modes, for
+layered MLP shapes and of the colour; for the normal maps also compositing from the render's own kept activations instead of a
+second forward, normals of the coarse or augmentation levels, normal losses or supervision, normals in the view sweep and the
+videos, and smoothing or bilateral filtering of depth normals.
 """
 from __future__ import annotations
 
@@ -95,9 +103,16 @@ def camera_matrices(camera: dict):
     return numpy.linalg.inv(camera_to_world), intrinsic.copy()
 
 
-def ply_bytes(points, colours) -> bytes:
+PLY_VERTEX_NORMAL = numpy.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4'),
+                                 ('red', 'u1'), ('green', 'u1'), ('blue', 'u1')])     # 27 bytes
+
+
+def ply_bytes(points, colours, normals=None) -> bytes:
     """A binary little-endian PLY file of N vertices: float x, y, z and uchar red, green, blue, 15 bytes a record.  ``points`` (N,3)
-    float32 and ``colours`` (N,3) uint8, tensors (copied to the host) or numpy; N = 0 is a valid file."""
+    float32 and ``colours`` (N,3) uint8, tensors (copied to the host) or numpy; N = 0 is a valid file.  With ``normals`` (N,3)
+    float32 the vertex element is ``x y z nx ny nz red green blue``, 27 bytes a record (oriented normals, as a surface
+    reconstruction reads them); without, the file is what it was before normals existed.  ``ply_mesh_bytes`` writes its vertex
+    element through this function."""
     if isinstance(points, torch.Tensor):
         points = points.detach().cpu().numpy()
     if isinstance(colours, torch.Tensor):
@@ -107,23 +122,33 @@ def ply_bytes(points, colours) -> bytes:
         raise RuntimeError(f'points: expected float32 (N, 3), got {points.dtype} {points.shape}')
     if colours.dtype != numpy.uint8 or colours.shape != points.shape:
         raise RuntimeError(f'colours: expected uint8 {points.shape}, got {colours.dtype} {colours.shape}')
-    records = numpy.empty((points.shape[0],), dtype=PLY_VERTEX)
+    if normals is not None:
+        if isinstance(normals, torch.Tensor):
+            normals = normals.detach().cpu().numpy()
+        normals = numpy.asarray(normals)
+        if normals.dtype != numpy.float32 or normals.shape != points.shape:
+            raise RuntimeError(f'normals: expected float32 {points.shape}, got {normals.dtype} {normals.shape}')
+    records = numpy.empty((points.shape[0],), dtype=PLY_VERTEX if normals is None else PLY_VERTEX_NORMAL)
     for a, name in enumerate(('x', 'y', 'z')):
         records[name] = points[:, a]
     for a, name in enumerate(('red', 'green', 'blue')):
         records[name] = colours[:, a]
+    if normals is not None:
+        for a, name in enumerate(('nx', 'ny', 'nz')):
+            records[name] = normals[:, a]
     header = ('ply\nformat binary_little_endian 1.0\n' + f'element vertex {points.shape[0]}\n'
               + 'property float x\nproperty float y\nproperty float z\n'
+              + ('' if normals is None else 'property float nx\nproperty float ny\nproperty float nz\n')
               + 'property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n')
     return header.encode('ascii') + records.tobytes()
 
 
-def save_ply(path, points, colours) -> None:
+def save_ply(path, points, colours, normals=None) -> None:
     """``ply_bytes`` written to ``path``.  A file that exists is left alone, as ``harness.save_video`` leaves it."""
     path = os.fspath(path)
     if os.path.exists(path):
         return
-    data = ply_bytes(points, colours)
+    data = ply_bytes(points, colours, normals)
     os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
     with open(path, 'wb') as f:
         f.write(data)
@@ -259,8 +284,47 @@ def field_normals(query_gradient, vertices: Tensor, ndc=None) -> Tensor:
     return ops.field_normals(vertices, grad, ndc)
 
 
-PLY_VERTEX_NORMAL = numpy.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4'),
-                                 ('red', 'u1'), ('green', 'u1'), ('blue', 'u1')])
+# ---------------------------------------------------------------------------------------------------------------- normal maps
+def ray_normals(query_gradient, rays_o: Tensor, rays_d: Tensor, z_vals: Tensor, weights: Tensor, ndc=None, min_weight: float = 0.0):
+    """-> (normals float32 (R,3), strength float32 (R), selected M) : the field's own normals composited along the rays of a render
+    with the render's weights.  The samples whose float32 (R,S) ``weights`` exceed ``min_weight`` are selected with the points the
+    MLP saw, ``rays_o`` + ``rays_d`` x ``z_vals`` in float32 (``ops.select_ray_samples``; the density's ReLU leaves exact zero weights
+    in empty space, and those samples cost no gradient); ``query_gradient`` -- any callable from float32 (n,3) device points, in the
+    space the model's MLP reads, to the float32 (n,3) gradient of the density there, as ``field_normals`` takes it -- is asked at
+    them once; and every ray sums weight x unit normal over its samples, in the scene frame (``ops.composite_normals``; ``ndc`` =
+    (cx, cy, near) for a render of NDC rays, whose ``rays_o``, ``rays_d`` and ``z_vals`` are the NDC ones).  ``normals`` is that
+    sum's direction and ``strength`` its length: at most the sum of the selected weights, less where the samples' normals disagree;
+    both 0 for a ray without a usable sample."""
+    offsets, sample, points = ops.select_ray_samples(rays_o, rays_d, z_vals, weights, min_weight)
+    count = int(points.shape[0])
+    if count > 0:
+        grad = query_gradient(points)
+        if not isinstance(grad, torch.Tensor) or grad.dtype != torch.float32 or tuple(grad.shape) != (count, 3):
+            raise RuntimeError(f'query_gradient: expected float32 gradients of shape ({count}, 3), got '
+                               f'{(grad.dtype, tuple(grad.shape)) if isinstance(grad, torch.Tensor) else type(grad).__name__}')
+    else:
+        grad = torch.empty((0, 3), dtype=torch.float32, device=points.device)
+    normals, strength = ops.composite_normals(points, grad, offsets, sample, weights, ndc)
+    return normals, strength, count
+
+
+def depth_normals(depth: Tensor, extrinsics, intrinsics, mask: Optional[Tensor] = None, edge_threshold: Optional[float] = None) -> Tensor:
+    """-> float32 (V,h,w,3) on the device: the unit normals of the float32 (V,h,w) ``depth`` maps on the GPU, in the scene frame and
+    facing their cameras, from the points of neighbouring pixels (``fuse_depth_maps``' points; ``ops.depth_normals`` has the rule).
+    ``mask`` and the validity of a pixel as in ``fuse_depth_maps``; with ``edge_threshold`` a neighbour whose depth differs by more
+    than ``edge_threshold`` x the pixel's depth is not differenced across.  (0, 0, 0) where no normal can be formed."""
+    return ops.depth_normals(depth, _views_of(depth, extrinsics, intrinsics), mask, edge_threshold)
+
+
+def normals_to_u8(normals: Tensor, camera: Optional[dict] = None) -> Tensor:
+    """-> uint8, the shape of the float32 (...,3) ``normals``: the picture of a normal map, 127.5 (c + 1) rounded, c the normal in
+    the frame of ``camera`` (a dict as ``harness.frame_batch`` takes it: its ``pose[:3, :3]``, camera-to-world, the camera looking
+    down -z with y up, so a surface that faces the camera comes out blue) or, without a camera, the scene frame.  A zero normal is
+    mid-grey (128, 128, 128)."""
+    rotation = None
+    if camera is not None:
+        rotation = numpy.asarray(camera['pose'], dtype=numpy.float64).reshape(4, 4)[:3, :3]
+    return ops.normals_to_u8(normals, rotation)
 
 
 def ply_mesh_bytes(points, colours, triangles, normals=None) -> bytes:
@@ -273,25 +337,9 @@ def ply_mesh_bytes(points, colours, triangles, normals=None) -> bytes:
     triangles = numpy.asarray(triangles)
     if triangles.dtype != numpy.int32 or triangles.ndim != 2 or triangles.shape[1] != 3:
         raise RuntimeError(f'triangles: expected int32 (F, 3), got {triangles.dtype} {triangles.shape}')
-    vertex_file = ply_bytes(points, colours)
+    vertex_file = ply_bytes(points, colours, normals)
     end = b'end_header\n'
     header, records = vertex_file.split(end, 1)
-    if normals is not None:
-        if isinstance(normals, torch.Tensor):
-            normals = normals.detach().cpu().numpy()
-        normals = numpy.asarray(normals)
-        plain = numpy.frombuffer(records, dtype=PLY_VERTEX)
-        if normals.dtype != numpy.float32 or normals.shape != (plain.shape[0], 3):
-            raise RuntimeError(f'normals: expected float32 {(plain.shape[0], 3)}, got {normals.dtype} {normals.shape}')
-        with_normals = numpy.empty(plain.shape, dtype=PLY_VERTEX_NORMAL)
-        for name in PLY_VERTEX.names:
-            with_normals[name] = plain[name]
-        for a, name in enumerate(('nx', 'ny', 'nz')):
-            with_normals[name] = normals[:, a]
-        records = with_normals.tobytes()
-        colour_properties = b'property uchar red\n'
-        before, after = header.split(colour_properties, 1)
-        header = before + b'property float nx\nproperty float ny\nproperty float nz\n' + colour_properties + after
     faces = numpy.empty((triangles.shape[0],), dtype=PLY_FACE)
     faces['count'] = 3
     for a, name in enumerate(('a', 'b', 'c')):

@@ -195,6 +195,82 @@ def predict_frame(model, configs: dict, camera: dict, device, rank: int = 0, wor
     return retrieve_inference_outputs(configs, camera['resolution'], frame)
 
 
+NORMALS_RAY_BLOCK = 1 << 14      # rays per block of predict_normals: see its docstring for the arithmetic
+
+
+def _gradient_field(what: str, model, configs: dict):
+    """(model unwrapped, the displayed level's MLP name) of a call that needs ``model.query_gradient``; raises what that would raise
+    -- NotImplementedError naming the limit, for a ``predict_visibility`` MLP and for a layered shape -- before the caller renders."""
+    model = getattr(model, 'module', model) if isinstance(model, torch.nn.DataParallel) else model
+    mlp = 'fine_mlp' if 'fine_mlp' in configs['model'] else 'coarse_mlp'
+    if not hasattr(model, 'check_query_gradient'):
+        raise NotImplementedError(f'{what}: the model has no query_gradient')
+    model.check_query_gradient(mlp)
+    return model, mlp
+
+
+@torch.no_grad()
+def predict_normals(model, configs: dict, camera: dict, device, ray_block: int = NORMALS_RAY_BLOCK, min_weight: float = 0.0,
+                    gradient_block: int = 1 << 16, edge_threshold: Optional[float] = None) -> dict:
+    """The two normal maps of a rendered frame, the standard picture for judging a NeRF's geometry.  The frame is rendered in blocks
+    of ``ray_block`` rays at the model's precision with ``retraw=True``, for the displayed level (the fine one when there is one).
+    Per block the samples whose weight exceeds ``min_weight`` are selected with the points the MLP saw (the NDC rays and depths for a
+    model of NDC rays), ``model.query_gradient`` gives the density's gradient there, and every ray sums weight x unit normal over its
+    samples (``geometry.ray_normals``).  ``query_gradient`` is ALWAYS fp32 on the master weights, whatever the model's
+    ``hip_precision``: a 16-bit model gets its own weights composited with the fp32 field's normals.  Then the depth normals of the
+    frame's own displayed depth map (``geometry.depth_normals`` with the camera's matrices; ``edge_threshold`` as there).  Where the
+    two maps disagree, the density is not a surface yet.
+
+    Returns device tensors: 'normal' float32 (h,w,3) and 'normal_strength' float32 (h,w) (the length of the weighted sum: at most
+    the sum of the selected weights), 'depth_normal' float32 (h,w,3), both in the scene frame; 'normal_image', 'depth_normal_image'
+    uint8 (h,w,3), the maps in the camera's frame as ``geometry.normals_to_u8`` draws them (for ``save_image`` / ``png_files`` /
+    ``save_video``); 'depth' float32 (h,w), the displayed depth; and 'selected_fraction', the share of the frame's samples that
+    were selected (a float).
+
+    A model that ``query_gradient`` refuses -- a layered MLP shape, ``predict_visibility`` -- is refused here with the same
+    NotImplementedError before anything is rendered.  A ``DataParallel`` wrapper is unwrapped.
+
+    ``ray_block``: a block holds the per-sample outputs of ``retraw`` for every level that runs -- alpha, visibility, weights, sigma
+    and three colour channels, 7 floats, and the depth: 32 bytes a sample.  A coarse level of 64 samples and a fine one of 64 + 128
+    are 256 samples, 8 KB a ray: the default 2^14 rays hold 128 MB, beside the at most ~1.3 GB of one gradient block of 2^16 points
+    (20 KB a point) and 16 bytes a selected sample for its index and point."""
+    from . import geometry
+    model, mlp = _gradient_field('predict_normals', model, configs)
+    if isinstance(ray_block, bool) or int(ray_block) != ray_block or int(ray_block) < 1:
+        raise RuntimeError(f'ray_block: expected an integer >= 1, got {ray_block}')
+    ndc = bool(configs['data_loader']['ndc'])
+    suffix = '_fine' if mlp == 'fine_mlp' else '_coarse'
+    h, w = (int(v) for v in camera['resolution'])
+    n = h * w
+    parameters = geometry.ndc_parameters(camera) if ndc else None
+    normal = torch.empty((n, 3), dtype=torch.float32, device=device)
+    strength = torch.empty((n,), dtype=torch.float32, device=device)
+    rgb = torch.empty((n, 3), dtype=torch.float32, device=device)
+    depth = torch.empty((n,), dtype=torch.float32, device=device)
+    selected = samples = 0
+    field = lambda points: model.query_gradient(points, mlp, gradient_block)['grad']
+    for start in range(0, n, int(ray_block)):
+        count = min(int(ray_block), n - start)
+        batch = frame_batch(camera, ndc, device, start, count)
+        out = model(batch, retraw=True)
+        weights = out[f'weights{suffix}'].reshape(count, -1)
+        z_vals = out[f'z_vals{suffix}'].reshape(count, -1)
+        rays_o, rays_d = (batch['rays_o_ndc'], batch['rays_d_ndc']) if ndc else (batch['rays_o'], batch['rays_d'])
+        normal[start:start + count], strength[start:start + count], kept = geometry.ray_normals(field, rays_o, rays_d, z_vals, weights,
+                                                                                                parameters, min_weight)
+        rgb[start:start + count] = out[f'rgb{suffix}'].reshape(count, 3)
+        depth[start:start + count] = out[f'depth{suffix}'].reshape(count)
+        selected += kept
+        samples += int(weights.numel())
+    depth = ops.to_display(rgb, depth)[1].reshape(h, w)        # the displayed depth: clipped at 0, as predict_frame shows it
+    extrinsic, intrinsic = geometry.camera_matrices(camera)
+    depth_normal = geometry.depth_normals(depth[None], [extrinsic], [intrinsic], None, edge_threshold)[0]
+    normal = normal.reshape(h, w, 3)
+    return {'normal': normal, 'normal_strength': strength.reshape(h, w), 'depth_normal': depth_normal,
+            'normal_image': geometry.normals_to_u8(normal, camera), 'depth_normal_image': geometry.normals_to_u8(depth_normal, camera),
+            'depth': depth, 'selected_fraction': selected / samples if samples else 0.0}
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # static-camera view sweep: the reference's start_testing_static_videos (one pose, the view directions of every camera of a path)
 SWEEP_ACTIVATION_BYTES = 8 << 30      # what the saved activations + sweep scratch of one ray block may take on the fast route
@@ -1095,9 +1171,26 @@ def _render_views(what: str, model, configs: dict, cameras, device, depth_range)
     return images, depths, [m[0] for m in matrices], [m[1] for m in matrices], mask
 
 
+def _field_normals_of(what: str, field, configs: dict, cameras, points: Tensor) -> Tensor:
+    """The unit outward normals of the density field at the float32 (N,3) scene-frame ``points`` of a geometry export:
+    ``geometry.field_normals`` with ``model.query_gradient`` (always fp32, blocks of 2^16 points) of the displayed level's MLP --
+    ``field`` is ``_gradient_field``'s (model, MLP name).  For a model of NDC rays the warp's (cx, cy, near) come from ``cameras[0]``,
+    and every camera must give the same, as ``export_density_mesh`` asks."""
+    from . import geometry
+    model, mlp = field
+    ndc = None
+    if bool(configs['data_loader']['ndc']):
+        ndc = geometry.ndc_parameters(cameras[0])
+        for i, camera in enumerate(cameras):
+            if geometry.ndc_parameters(camera) != ndc:
+                raise RuntimeError(f'{what}: ndc: camera {i} has (cx, cy, near) = {geometry.ndc_parameters(camera)}, camera 0 has {ndc}; '
+                                   f'one NDC warp needs cameras of one resolution, focal length and near plane')
+    return geometry.field_normals(lambda q: model.query_gradient(q, mlp, 1 << 16)['grad'], points, ndc)
+
+
 @torch.no_grad()
 def export_point_cloud(model, configs: dict, cameras, path, device, depth_error_threshold: float = 0.02, min_views: int = 1,
-                       voxel_size: Optional[float] = None, depth_range=None) -> dict:
+                       voxel_size: Optional[float] = None, depth_range=None, normals: bool = False) -> dict:
     """The model's geometry as a point cloud: every camera of ``cameras`` (dicts as ``frame_batch`` takes them, one resolution)
     rendered as ``predict_frame`` renders it -- the 8-bit image and the depth stay on the device --, the depth maps fused
     (``geometry.fuse_depth_maps``: a pixel's point is kept where at least ``min_views`` other views agree with it to
@@ -1106,21 +1199,32 @@ def export_point_cloud(model, configs: dict, cameras, path, device, depth_error_
     only pixels with lo <= depth <= hi are sources or witnesses.  The cloud is in the model's processed scene frame (recentred, and
     scaled by ``translation_scale``); mapping it back to the data set's frame is the caller's.  Returns {'points' float32 (N,3),
     'colours' uint8 (N,3), 'counts' (N): the agreeing views of each point (uint8), or with ``voxel_size`` the points of each voxel
-    (int32), 'fused_points': N before thinning, 'images_device' (V,h,w,3), 'depths_device' (V,h,w)}, tensors on the device."""
+    (int32), 'fused_points': N before thinning, 'images_device' (V,h,w,3), 'depths_device' (V,h,w)}, tensors on the device.
+    ``normals=True`` adds 'normals' float32 (N,3): the unit outward normals of the density field at the written points (after the
+    thinning; ``_field_normals_of``), and the file's vertices carry them (``x y z nx ny nz red green blue``, 27 bytes a vertex:
+    oriented normals, which a Poisson reconstruction needs); the default writes the same bytes as before.  A model that
+    ``query_gradient`` refuses is refused before anything is rendered."""
     from . import geometry
+    cameras = list(cameras)
+    field = _gradient_field('export_point_cloud', model, configs) if normals else None
     images, depths, extrinsics, intrinsics, mask = _render_views('export_point_cloud', model, configs, cameras, device, depth_range)
     points, colours, counts = geometry.fuse_depth_maps(depths, images, extrinsics, intrinsics, depth_error_threshold, min_views, mask)
     fused = int(points.shape[0])
     if voxel_size is not None:
         points, colours, counts = geometry.voxel_thin(points, colours, voxel_size)
-    geometry.save_ply(path, points, colours)
-    return {'points': points, 'colours': colours, 'counts': counts, 'fused_points': fused, 'images_device': images,
-            'depths_device': depths}
+    out = {'points': points, 'colours': colours, 'counts': counts, 'fused_points': fused, 'images_device': images,
+           'depths_device': depths}
+    if normals:
+        out['normals'] = _field_normals_of('export_point_cloud', field, configs, cameras, points)
+        geometry.save_ply(path, points, colours, out['normals'])
+    else:
+        geometry.save_ply(path, points, colours)
+    return out
 
 
 @torch.no_grad()
 def export_mesh(model, configs: dict, cameras, path, device, voxel_size: float, truncation: Optional[float] = None, bounds=None,
-                min_weight: int = 1, colour_tolerance: Optional[float] = None, depth_range=None) -> dict:
+                min_weight: int = 1, colour_tolerance: Optional[float] = None, depth_range=None, normals: bool = False) -> dict:
     """The model's geometry as a triangle mesh: every camera of ``cameras`` rendered as ``export_point_cloud`` renders it, the depth
     maps fused into a truncated signed distance volume of ``voxel_size`` (``geometry.tsdf_volume``; ``truncation`` defaults to four
     voxels), the surface extracted by marching tetrahedra over the cells that at least ``min_weight`` views observed at every corner
@@ -1130,8 +1234,14 @@ def export_mesh(model, configs: dict, cameras, path, device, voxel_size: float, 
     by the truncation.  ``depth_range`` = (lo, hi): only pixels with lo <= depth <= hi are used.  Raises, naming the limit
     7 nx ny nz <= 2^31 - 1, when the grid is too large.  The mesh is in the model's processed scene frame.  Returns {'vertices'
     float32 (Nv,3), 'colours' uint8 (Nv,3), 'views' uint8 (Nv), 'triangles' int32 (Nt,3), 'tsdf' float32 (nz,ny,nx), 'weight' uint8
-    (nz,ny,nx), 'lo', 'voxel_size', 'extents' (nx,ny,nz), 'truncation', 'images_device', 'depths_device'}, tensors on the device."""
+    (nz,ny,nx), 'lo', 'voxel_size', 'extents' (nx,ny,nz), 'truncation', 'images_device', 'depths_device'}, tensors on the device.
+    ``normals=True`` adds 'normals' float32 (Nv,3): the unit outward normals of the density field at the vertices
+    (``_field_normals_of``, as ``export_density_mesh`` has them), and the file's vertices carry them (``x y z nx ny nz red green
+    blue``); the default writes the same bytes as before.  A model that ``query_gradient`` refuses is refused before anything is
+    rendered."""
     from . import geometry
+    cameras = list(cameras)
+    field = _gradient_field('export_mesh', model, configs) if normals else None
     voxel_size = float(voxel_size)
     if not (voxel_size > 0.0 and math.isfinite(voxel_size)):
         raise RuntimeError(f'export_mesh: voxel_size: expected a finite number > 0, got {voxel_size}')
@@ -1154,9 +1264,14 @@ def export_mesh(model, configs: dict, cameras, path, device, voxel_size: float, 
     tsdf, weight = geometry.tsdf_volume(depths, extrinsics, intrinsics, lo, voxel_size, extents, truncation, mask)
     vertices, triangles = geometry.extract_mesh(tsdf, weight, lo, voxel_size, min_weight)
     colours, views = geometry.colour_points(vertices, depths, images, extrinsics, intrinsics, colour_tolerance, mask)
-    geometry.save_ply_mesh(path, vertices, colours, triangles)
-    return {'vertices': vertices, 'colours': colours, 'views': views, 'triangles': triangles, 'tsdf': tsdf, 'weight': weight, 'lo': lo,
-            'voxel_size': voxel_size, 'extents': extents, 'truncation': truncation, 'images_device': images, 'depths_device': depths}
+    out = {'vertices': vertices, 'colours': colours, 'views': views, 'triangles': triangles, 'tsdf': tsdf, 'weight': weight, 'lo': lo,
+           'voxel_size': voxel_size, 'extents': extents, 'truncation': truncation, 'images_device': images, 'depths_device': depths}
+    if normals:
+        out['normals'] = _field_normals_of('export_mesh', field, configs, cameras, vertices)
+        geometry.save_ply_mesh(path, vertices, colours, triangles, out['normals'])
+    else:
+        geometry.save_ply_mesh(path, vertices, colours, triangles)
+    return out
 
 
 @torch.no_grad()

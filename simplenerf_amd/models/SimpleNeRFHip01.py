@@ -415,6 +415,23 @@ class SimpleNeRFHip(torch.nn.Module):
             out['rgb'] = rgb
         return out
 
+    def check_query_gradient(self, mlp: Optional[str] = None, shapes: bool = True) -> 'MlpParameters':
+        """The refusals of ``query_gradient`` without a point and without a launch: -> the module of MLP ``mlp``, or KeyError for a
+        name the model has no MLP under, NotImplementedError naming the limit for a ``predict_visibility`` MLP and for one of the
+        layered path's shapes (``shapes=False``: not that one).  For a caller that would render first (``harness.predict_normals``)."""
+        if mlp is None:
+            mlp = 'fine_mlp' if self.fine_mlp_needed else 'coarse_mlp'
+        names = {'coarse_mlp': 'coarse_model', 'fine_mlp': 'fine_model' if self.fine_mlp_needed else None}
+        if names.get(mlp) is None:
+            raise KeyError(f"mlp: expected one of {sorted(k for k, v in names.items() if v)}, got {mlp!r}")
+        module: MlpParameters = getattr(self, names[mlp])
+        if module.predict_visibility:
+            raise NotImplementedError('query_gradient: predict_visibility MLPs are not built for point queries (their views head has '
+                                      'a fourth output the forward kernels do not return)')
+        if shapes:
+            ops.check_input_gradient(module.mlp_configs)
+        return module
+
     @torch.no_grad()
     def query_gradient(self, points: Tensor, mlp: Optional[str] = None, point_block: int = 1 << 16) -> Dict[str, Tensor]:
         """The density and its gradient with respect to the point: {'sigma' (N,), 'grad' (N,3)} of MLP ``mlp`` at the float32 (N,3)
@@ -432,12 +449,7 @@ class SimpleNeRFHip(torch.nn.Module):
         if mlp is None:
             mlp = 'fine_mlp' if self.fine_mlp_needed else 'coarse_mlp'
         names = {'coarse_mlp': 'coarse_model', 'fine_mlp': 'fine_model' if self.fine_mlp_needed else None}
-        if names.get(mlp) is None:
-            raise KeyError(f"mlp: expected one of {sorted(k for k, v in names.items() if v)}, got {mlp!r}")
-        module: MlpParameters = getattr(self, names[mlp])
-        if module.predict_visibility:
-            raise NotImplementedError('query_gradient: predict_visibility MLPs are not built for point queries (their views head has '
-                                      'a fourth output the forward kernels do not return)')
+        module = self.check_query_gradient(mlp, shapes=False)      # (a layered shape is refused below, before anything is packed)
         if isinstance(point_block, bool) or int(point_block) != point_block or int(point_block) < 1:
             raise RuntimeError(f'point_block: expected an integer >= 1, got {point_block}')
         points = ops._dev(points, 'points')

@@ -347,6 +347,16 @@ class PackedMlp:
         return out
 
 
+def check_input_gradient(mlp_cfg: dict) -> None:
+    """Raises NotImplementedError, naming the limit, for an MLP config ``PackedMlp.input_gradient`` is not built for (a layered
+    shape, ``predict_visibility``): the descriptor's own check on the host, without a device buffer or a launch."""
+    lib = _lib.load()
+    desc = mlp_desc(mlp_cfg)
+    if int(lib.snerf_mlp_input_gradient_workspace_floats(ctypes.byref(desc), 1)) == 0:
+        msg = lib.snerf_last_error()
+        raise NotImplementedError(msg.decode() if msg else 'mlp_input_gradient: not built for this MLP')
+
+
 # ---------------------------------------------------------------------------------------------- one-call render ops
 PER_SAMPLE_BITS = {'alpha': 1, 'visibility': 2, 'weights': 4}     # the per-sample request mask of snerf_render_layout_query
 
@@ -1479,6 +1489,120 @@ def field_normals(points: Tensor, grad: Tensor, ndc=None) -> Tensor:
     if n > 0:
         _enqueue('snerf_field_normals', dev, _ptr(points), _ptr(grad), n, *flag, _ptr(normals))
     return normals
+
+
+# ---------------------------------------------------------------------------------------------- Q10 normal maps
+def _ndc_flag(ndc) -> tuple:
+    """(0, 0, 0, 0) or (1, cx, cy, near): THE INPUT MAP's arguments of a C call, checked as ``field_normals`` checks them."""
+    if ndc is None:
+        return (0, 0.0, 0.0, 0.0)
+    ndc = tuple(float(v) for v in ndc)
+    if len(ndc) != 3 or not all(math.isfinite(v) for v in ndc) or not ndc[2] > 0.0:
+        raise RuntimeError(f'ndc: expected None or three finite numbers (cx, cy, near) with near > 0, got {ndc}')
+    return (1,) + ndc
+
+
+def _ray_samples(weights, min_weight):
+    weights = _typed(weights, 'weights', (torch.float32,))
+    if weights.dim() != 2:
+        raise RuntimeError(f'weights: expected shape (rays, samples), got {tuple(weights.shape)}')
+    rays, samples = (int(s) for s in weights.shape)
+    if rays * samples > SORT_MAX_COUNT:
+        raise RuntimeError(f'weights: {rays} rays of {samples} samples exceed the 2^31 - 1 samples the kernels index')
+    min_weight = float(min_weight)
+    if math.isnan(min_weight):
+        raise RuntimeError('min_weight: expected a number, got nan')
+    return weights, rays, samples, min_weight
+
+
+def select_ray_samples(rays_o: Tensor, rays_d: Tensor, z_vals: Tensor, weights: Tensor, min_weight: float = 0.0):
+    """-> (offsets int32 (R+1), sample int32 (M), points float32 (M,3)) on the device: the samples of a render whose float32 (R,S)
+    ``weights`` exceed ``min_weight`` (a NaN weight is not selected), in ascending flat index r S + i (``sample``), with the points
+    ``rays_o`` + ``rays_d`` x ``z_vals`` evaluated in float32 exactly as the render kernels evaluate them -- the points the MLP saw;
+    ``offsets`` is the exclusive prefix of the per-ray counts, ``offsets[R]`` = M (csrc/simplenerf_normals.h has the rule).
+    ``rays_o``, ``rays_d`` float32 (R,3), ``z_vals`` float32 (R,S): the rays the render marched, the NDC rays and depths of an NDC
+    render.  Count, read M back (the one synchronisation), allocate, emit."""
+    weights, rays, samples, min_weight = _ray_samples(weights, min_weight)
+    rays_o = _typed(rays_o, 'rays_o', (torch.float32,), (rays, 3))
+    rays_d = _typed(rays_d, 'rays_d', (torch.float32,), (rays, 3))
+    z_vals = _typed(z_vals, 'z_vals', (torch.float32,), (rays, samples))
+    dev = weights.device
+    _warp_together(dev, rays_o=rays_o, rays_d=rays_d, z_vals=z_vals)
+    offsets = torch.empty((rays + 1,), dtype=torch.int32, device=dev)
+    _enqueue('snerf_ray_samples_count', dev, _ptr(weights), rays, samples, min_weight, _ptr(offsets))
+    count = int(offsets[rays].item())
+    sample = torch.empty((count,), dtype=torch.int32, device=dev)
+    points = torch.empty((count, 3), dtype=torch.float32, device=dev)
+    if count > 0:
+        _enqueue('snerf_ray_samples_emit', dev, _ptr(rays_o), _ptr(rays_d), _ptr(z_vals), _ptr(weights), rays, samples, min_weight,
+                 _ptr(offsets), count, _ptr(sample), _ptr(points))
+    return offsets, sample, points
+
+
+def composite_normals(points: Tensor, grad: Tensor, offsets: Tensor, sample: Tensor, weights: Tensor, ndc=None):
+    """-> (normal float32 (R,3), strength float32 (R)) on the device: per ray the weighted sum, over its selected samples
+    (``offsets``, ``sample``, ``points`` of ``select_ray_samples``), of the field's unit normals -G / |G| there, G the float32 (M,3)
+    gradient ``grad`` of the density at the points (``model.query_gradient``) pulled back through the input map (``ndc`` = None: the
+    identity; (cx, cy, near): the NDC warp, inverted to find the scene point); ``strength`` is the sum's length, ``normal`` the sum
+    over it, and both are 0 where it is 0 or not finite.  Sequential float64 sums in sample order (csrc/simplenerf_normals.h has the
+    rule).  ``weights`` float32 (R,S): the render's."""
+    weights, rays, samples, _ = _ray_samples(weights, 0.0)
+    offsets = _typed(offsets, 'offsets', (torch.int32,), (rays + 1,))
+    sample = _typed(sample, 'sample', (torch.int32,))
+    if sample.dim() != 1:
+        raise RuntimeError(f'sample: expected shape (M,), got {tuple(sample.shape)}')
+    count = int(sample.shape[0])
+    points = _typed(points, 'points', (torch.float32,), (count, 3))
+    grad = _typed(grad, 'grad', (torch.float32,), (count, 3))
+    flag = _ndc_flag(ndc)
+    dev = weights.device
+    _warp_together(dev, points=points, grad=grad, offsets=offsets, sample=sample)
+    normal = torch.empty((rays, 3), dtype=torch.float32, device=dev)
+    strength = torch.empty((rays,), dtype=torch.float32, device=dev)
+    if rays > 0:
+        _enqueue('snerf_composite_normals', dev, _ptr(points), _ptr(grad), count, _ptr(offsets), _ptr(sample), _ptr(weights), rays, samples,
+                 *flag, _ptr(normal), _ptr(strength))
+    return normal, strength
+
+
+def depth_normals(depth: Tensor, cameras: Tensor, mask: Optional[Tensor] = None, edge_threshold: Optional[float] = None) -> Tensor:
+    """-> float32 (V,h,w,3) on the device: the unit normals of the float32 (V,h,w) ``depth`` maps in the scene frame, facing their
+    cameras: the cross product of a pixel's horizontal and vertical tangents, each the difference of the neighbouring pixels' points
+    (``fuse_depth_maps``' own points; central where both neighbours are usable, one-sided with one).  A pixel is valid as in the fuse
+    (finite positive depth, ``mask`` set); a neighbour is usable when it is valid and, with ``edge_threshold``, its depth differs
+    from the pixel's by at most ``edge_threshold`` x the pixel's.  (0, 0, 0) for an invalid pixel, a missing tangent or a degenerate
+    cross product (csrc/simplenerf_normals.h has the rule).  ``cameras``: float64 (V,42) (``geometry.fuse_cameras``)."""
+    depth, cameras, mask, _, views, h, w = _mesh_views(depth, cameras, mask)
+    edge = -1.0 if edge_threshold is None else float(edge_threshold)
+    if edge_threshold is not None and not edge >= 0.0:
+        raise RuntimeError(f'edge_threshold: expected None or a non-negative number, got {edge_threshold}')
+    dev = depth.device
+    normals = torch.empty((views, h, w, 3), dtype=torch.float32, device=dev)
+    if views * h * w > 0:
+        _enqueue('snerf_depth_normals', dev, _ptr(depth), _ptr(mask), _ptr(cameras), views, h, w, edge, _ptr(normals))
+    return normals
+
+
+def normals_to_u8(normals: Tensor, rotation=None) -> Tensor:
+    """-> uint8, the shape of ``normals``: float32 (...,3) unit normals as a picture, min(255, max(0, floor(127.5 (c + 1) + 0.5)))
+    of c = R^T n for the 3x3 ``rotation`` R (a camera-to-world rotation: the picture is in the camera's frame; None: the identity).
+    A zero normal is (128, 128, 128), a NaN 0 (csrc/simplenerf_normals.h has the rule)."""
+    normals = _typed(normals, 'normals', (torch.float32,))
+    if normals.dim() < 1 or normals.shape[-1] != 3:
+        raise RuntimeError(f'normals: expected shape (..., 3), got {tuple(normals.shape)}')
+    count = normals.numel() // 3
+    if count > SORT_MAX_COUNT:
+        raise RuntimeError(f'normals: {count} normals exceed the 2^31 - 1 the kernels index')
+    table = None
+    if rotation is not None:
+        matrix = numpy.asarray(rotation.detach().cpu().numpy() if isinstance(rotation, torch.Tensor) else rotation, dtype=numpy.float64)
+        if matrix.shape != (3, 3) or not numpy.isfinite(matrix).all():
+            raise RuntimeError(f'rotation: expected None or a finite 3x3 matrix, got shape {matrix.shape}')
+        table = (ctypes.c_double * 9)(*matrix.reshape(-1).tolist())
+    image = torch.empty(normals.shape, dtype=torch.uint8, device=normals.device)
+    if count > 0:
+        _enqueue('snerf_normals_to_u8', normals.device, _ptr(normals), count, table, _ptr(image))
+    return image
 
 
 # ---------------------------------------------------------------------------------------------- f1 losses
